@@ -17,7 +17,14 @@ process per GPU, no collective on the data path, RANSAC keyed by (seed, a, b, h)
 not depend on the sharding).  value = verified matches of the whole graph per step * steps /
 max-over-ranks wall time.
 
-Also reported (rank 0): `roofline` of K1 (algorithmic 2*Ka*Kb*128 i8 ops per pair over the K1
+A plain run (`--gpus N --steps K --warmup W`) builds the scene, warms up, times the K steps and
+prints the line: metric / value / unit / ms_per_step, the workload, the graph's size and checksum
+and the stage times (HIP events on the launch stream).  `--dump-outputs DIR` also writes what the
+last timed step returned (graph_outputs; for cfg5 the reconstruction) as DIR/<name>.npy; the
+scenes are seeded, so two builds can be compared array for array.  Everything below runs only
+with `--full`.
+
+With `--full` also reported (rank 0): `roofline` of K1 (algorithmic 2*Ka*Kb*128 i8 ops per pair over the K1
 time measured with HIP events on the launch stream, against the dense i8 MFMA peak), the RANSAC
 stage against the f32 vector peak (algorithmic and executed evaluations), `cpu_baseline` (N = 1):
 the CPU oracle (oracle/, OpenMP over pairs) timed on a bounded stride sample of the same pairs on
@@ -29,8 +36,9 @@ the north_star's 2048 x 128 K1 kernel and the cfg3 step, measured in the same ru
 `--config cfg5` (BASELINE configs[4]): full incremental SfM on a 500 x 4096 synthetic scene
 (incremental.reconstruct: match + verify sharded over the ranks with the graph all-gathered, tracks,
 registration, triangulation, LM bundle adjustment with the camera blocks all-reduced and the PCG
-sharded or replicated by reconstruction.pcg_rule); a step = one whole reconstruction.  Every N = 1
-cfg4 line carries a `cfg5` object measured in the same run.
+sharded or replicated by reconstruction.pcg_rule); a step = one whole reconstruction; `--full` adds
+the K3 / CG-iteration rooflines on the final model.  Every `--full` cfg4 line carries a `cfg5`
+object measured in the same run.
 
 Launch: `--gpus N` with no external launcher (WORLD_SIZE unset) starts N fresh rank processes
 itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / a free MASTER_PORT, rank r on GPU
@@ -186,6 +194,15 @@ def parse_args(argv=None):
                     help="pairs per K1/K2 launch (default: a cfg4 shard in one launch, ~90 GB of "
                          "buffers at N = 1; same graph checksum as 16384-pair chunks, 1.7-2.2 %% "
                          "faster, profiles/r02/bench_chunk_ab.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps also run everything else this benchmark "
+                         "measures or checks: roofline figures (calib probe, K2 executed-work "
+                         "counters), CPU baselines + parity, fp64 K2, the cfg2 / cfg3 / cfg4_local / "
+                         "cfg5 legs, the BA rooflines of --config cfg5 (each still has its --no-* "
+                         "switch).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB in all; rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="CPU baseline budget (the sample is sized to about this much wall)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -360,6 +377,9 @@ def launch_ranks(args, argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        log("bench.py: --steps must be >= 1 and --warmup >= 0")
+        return 2
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if args.gpus > 1:
@@ -445,16 +465,20 @@ def pairs_main(args, world, rank, local, dist_info):
     # K2's executed share is measured in the timed steps themselves (sfm_ransac_stats: one u32
     # store per score wave + one small reduction kernel per launch, ~10 us at cfg4).  Enabled
     # before the warm-up so the workspace that holds the per-wave counts is sized there; the
-    # read below resets the counters before the timed region.
-    run.ctx.ransac_stats(enable=True)
+    # read below resets the counters before the timed region.  --full only: a plain run times
+    # the steps without the counters and without the calib probe.
+    if args.full:
+        run.ctx.ransac_stats(enable=True)
     for _ in range(args.warmup):
         run.step(xr)
     torch.cuda.synchronize()
-    run.ctx.ransac_stats(enable=True, read=True)
-    # this box's i8 matrix ceiling, measured in the same run right before the
-    # timed steps (an MFMA-only launch of ~200 ms on every CU), so K1's fraction can be read
-    # against the box it ran on; not inside the timed region
-    calib = run.ctx.calib_mfma_i8(200.0)
+    calib = None
+    if args.full:
+        run.ctx.ransac_stats(enable=True, read=True)
+        # this box's i8 matrix ceiling, measured in the same run right before
+        # the timed steps (an MFMA-only launch of ~200 ms on every CU), so K1's fraction can be
+        # read against the box it ran on; not inside the timed region
+        calib = run.ctx.calib_mfma_i8(200.0)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -475,16 +499,14 @@ def pairs_main(args, world, rank, local, dist_info):
 
     verified_per_step = int(graph.shape[0])
     checksum = graph_checksum(torch, graph)  # after the timed region
-    r_alg, r_exec, r_evals = ransac_flops(run.ctx.ransac_stats(enable=False, read=True),
-                                          args.n_hyp, args.steps)
     st = [Runner.stage_ms(e) for e in evs]
     match_ms = float(np.mean([s[0] for s in st]))
     ransac_ms = float(np.mean([s[1] for s in st]))
     per_rank = gather_ranks(world, {
         "rank": rank, "device": local, "pairs": int(hi - lo),
         "shard_ms_per_step": t_own / args.steps * 1e3, "match_ms": match_ms,
-        "ransac_ms": ransac_ms, "calib_tops": calib["tops"], "calib_clock_ghz": calib["clock_ghz"]})
-    k1_tops = run.k1_ops / (match_ms * 1e-3) / 1e12
+        "ransac_ms": ransac_ms, "calib_tops": calib["tops"] if calib else None,
+        "calib_clock_ghz": calib["clock_ghz"] if calib else None})
     value = verified_per_step * args.steps / elapsed
     result = {
         "metric": "verified matches/sec (match+RANSAC)",
@@ -499,6 +521,7 @@ def pairs_main(args, world, rank, local, dist_info):
         "vs_baseline": None,
         "dtype": "int8 MFMA -> exact int32 (K1), f32 (K2)",
         "data": "synthetic (seeded scene: SIFT-like u8 descriptors, 25% misplaced keypoints)",
+        "full": bool(args.full),
         "config": {
             "workload": workload_string(args.config, n_img, k, args.n_hyp, args.chunk),
             "baseline_config": cfg["name"], "n_img": n_img, "k": k, "n_hyp": args.n_hyp,
@@ -508,47 +531,57 @@ def pairs_main(args, world, rank, local, dist_info):
         "distributed": dict(dist_info, per_rank=per_rank),
         "verified_matches_per_step": verified_per_step,
         "graph_checksum": checksum,
-        "roofline": {"kernel": "K1 L2 match, mutual rule (mfma_prep + mfma_mutual_kernel + "
-                               "mutual_finalize, HIP events on the launch stream, rank 0)",
-                     "bound": "mfma", "achieved": k1_tops, "peak": PEAK_I8_TOPS,
-                     "unit": "TOP/s (i8)", "frac": k1_tops / PEAK_I8_TOPS,
-                     "traffic": pmc_traffic("mfma_mutual_kernel", args.config, n_img, k, world),
-                     "traffic_unit": f"HBM bytes per step (all launches), PMC, "
-                                     f"profiles/traffic_{args.config}.json",
-                     "ms": match_ms, "ops_per_step": run.k1_ops,
-                     "practical_peak": calib["tops"],
-                     "frac_of_practical": k1_tops / calib["tops"],
-                     "practical_peak_note": "this run's calib probe (below): an i8 MFMA-only launch "
-                                            "on random operands on every CU of this box",
-                     "practical_peak_recorded": PRACTICAL_I8_TOPS},
-        "calib": dict(calib, probe="sfm_calib_mfma_i8: v_mfma_i32_32x32x32_i8 on register "
-                                   "operands, random data, 2 waves per SIMD on every CU, ~200 ms, "
-                                   "run right before the timed steps (rank 0's device)",
-                      nominal_tops=PEAK_I8_TOPS),
         "stages": {"match_ms": match_ms, "ransac_ms": ransac_ms,
-                   "graph_ms": elapsed / args.steps * 1e3 - match_ms - ransac_ms,
-                   "ransac_roofline": {
-                       "bound": "f32 VALU", "peak": PEAK_F32_VALU_TFLOPS, "unit": "TFLOP/s",
-                       "achieved": r_alg * r_exec / (ransac_ms * 1e-3) / 1e12,
-                       "frac": r_alg * r_exec / (ransac_ms * 1e-3) / 1e12 / PEAK_F32_VALU_TFLOPS,
-                       "executed_flops_per_step": r_alg * r_exec,
-                       "algorithmic_flops_per_step": r_alg,
-                       "executed_frac": r_exec,
-                       "evaluations_per_step": r_evals,
-                       "executed_counts_masked_lanes": True,
-                       "note": "achieved / frac count the EXECUTED work (the exact pruning skips "
-                               "the rest): Sampson evaluations counted by the score waves in the "
-                               "timed steps (sfm_ransac_stats) x 33 flop + 1400 flop per fitted "
-                               "hypothesis; algorithmic = every hypothesis on every match "
-                               "(pairs with >= 8 matches); executed_frac = executed / algorithmic. "
-                               "executed = ISSUED lane-slots (a score wave runs until its last "
-                               "live lane stops: lanes already pruned count as masked slots; plus "
-                               "the final kernel's M per pair), so frac is an issue-slot figure, "
-                               "an upper bound on useful-work utilisation",
-                       "practical_peak": PRACTICAL_F32_VALU_TFLOPS,
-                       "frac_of_practical":
-                           r_alg * r_exec / (ransac_ms * 1e-3) / 1e12 / PRACTICAL_F32_VALU_TFLOPS}},
+                   "graph_ms": elapsed / args.steps * 1e3 - match_ms - ransac_ms},
     }
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, graph_outputs(torch, graph, len(pairs)))
+    if not args.full:
+        return result
+
+    r_alg, r_exec, r_evals = ransac_flops(run.ctx.ransac_stats(enable=False, read=True),
+                                          args.n_hyp, args.steps)
+    k1_tops = run.k1_ops / (match_ms * 1e-3) / 1e12
+    result["roofline"] = {
+        "kernel": "K1 L2 match, mutual rule (mfma_prep + mfma_mutual_kernel + "
+                  "mutual_finalize, HIP events on the launch stream, rank 0)",
+        "bound": "mfma", "achieved": k1_tops, "peak": PEAK_I8_TOPS,
+        "unit": "TOP/s (i8)", "frac": k1_tops / PEAK_I8_TOPS,
+        "traffic": pmc_traffic("mfma_mutual_kernel", args.config, n_img, k, world),
+        "traffic_unit": f"HBM bytes per step (all launches), PMC, "
+                        f"profiles/traffic_{args.config}.json",
+        "ms": match_ms, "ops_per_step": run.k1_ops,
+        "practical_peak": calib["tops"],
+        "frac_of_practical": k1_tops / calib["tops"],
+        "practical_peak_note": "this run's calib probe (below): an i8 MFMA-only launch "
+                               "on random operands on every CU of this box",
+        "practical_peak_recorded": PRACTICAL_I8_TOPS}
+    result["calib"] = dict(calib, probe="sfm_calib_mfma_i8: v_mfma_i32_32x32x32_i8 on register "
+                                        "operands, random data, 2 waves per SIMD on every CU, "
+                                        "~200 ms, run right before the timed steps (rank 0's "
+                                        "device)",
+                           nominal_tops=PEAK_I8_TOPS)
+    result["stages"]["ransac_roofline"] = {
+        "bound": "f32 VALU", "peak": PEAK_F32_VALU_TFLOPS, "unit": "TFLOP/s",
+        "achieved": r_alg * r_exec / (ransac_ms * 1e-3) / 1e12,
+        "frac": r_alg * r_exec / (ransac_ms * 1e-3) / 1e12 / PEAK_F32_VALU_TFLOPS,
+        "executed_flops_per_step": r_alg * r_exec,
+        "algorithmic_flops_per_step": r_alg,
+        "executed_frac": r_exec,
+        "evaluations_per_step": r_evals,
+        "executed_counts_masked_lanes": True,
+        "note": "achieved / frac count the EXECUTED work (the exact pruning skips "
+                "the rest): Sampson evaluations counted by the score waves in the "
+                "timed steps (sfm_ransac_stats) x 33 flop + 1400 flop per fitted "
+                "hypothesis; algorithmic = every hypothesis on every match "
+                "(pairs with >= 8 matches); executed_frac = executed / algorithmic. "
+                "executed = ISSUED lane-slots (a score wave runs until its last "
+                "live lane stops: lanes already pruned count as masked slots; plus "
+                "the final kernel's M per pair), so frac is an issue-slot figure, "
+                "an upper bound on useful-work utilisation",
+        "practical_peak": PRACTICAL_F32_VALU_TFLOPS,
+        "frac_of_practical":
+            r_alg * r_exec / (ransac_ms * 1e-3) / 1e12 / PRACTICAL_F32_VALU_TFLOPS}
     # step-level fraction = sum of the stages' roofline times / measured step time
     # (K1 at the dense-i8 peak; K2 at the f32 VALU peak on the executed share of the work)
     t_k1 = run.k1_ops / (PEAK_I8_TOPS * 1e12)
@@ -652,13 +685,15 @@ def cfg4_local_side(n_img, k, n_hyp, chunk, steps=3, warmup=1):
             "graph_checksum": graph_checksum(torch, graph)}
 
 
-def cfg5_run(n_img, k, n_pts, steps, warmup, world, rank, local, pcg):
+def cfg5_run(n_img, k, n_pts, steps, warmup, world, rank, local, pcg, rooflines=True,
+             dump_dir=None):
     """BASELINE configs[4]: `steps` whole incremental reconstructions of the cfg5 scene (seeded:
     CFG5_SEED, k1 in +-0.02, visibility window CFG5_WINDOW, n_pts 3-D points or the window's
     default) timed between barriers (max over ranks), after `warmup` reconstructions of the first
     4 views.  Returns the measurement dict (rank 0's
     view; quality against the scene's truth, BA sizes / iterations / PCG branch, and the K3 and
-    CG-iteration HBM fractions on the final bundle adjustment's problem)."""
+    CG-iteration HBM fractions on the final bundle adjustment's problem when `rooflines`).
+    `dump_dir`: rank 0 writes the last reconstruction there (dump_outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -743,7 +778,15 @@ def cfg5_run(n_img, k, n_pts, steps, warmup, world, rank, local, pcg):
                            "busbw_GBs_last": rules[-1]["busbw_GBs"],
                            "branch_counts": {m: sum(b["pcg"] == m for b in rec.ba_log)
                                              for m in ("sharded", "replicated")}}
-    if rank == 0:
+    if rank == 0 and dump_dir:
+        dump_outputs(dump_dir, {
+            "registered": reg.astype(np.float32),
+            "cams": np.where(reg[:, None], rec.cams, 0.0).astype(np.float64),
+            "has_point": rec.has_point.astype(np.float32),
+            "points": np.where(rec.has_point[:, None], rec.points, 0.0).astype(np.float64),
+            "summary": np.array([rec.n_verified, reg.sum(), rec.has_point.sum(), use.sum()],
+                                np.float64)})
+    if rank == 0 and rooflines:
         out["ba_rooflines"] = ba_rooflines(scene["pp"], rec.cams, rec.points[pts_ids],
                                            timg[use].astype(np.int32), pt_idx, uv, local)
     return out
@@ -878,7 +921,7 @@ def cfg5_main(args, world, rank, local, dist_info):
     n_img = args.n_img or cfg["n_img"]
     k = args.k or cfg["k"]
     r = cfg5_run(n_img, k, args.n_pts or None, args.steps, args.warmup, world, rank, local,
-                 args.ba_pcg)
+                 args.ba_pcg, rooflines=args.full, dump_dir=args.dump_outputs)
     n_pts = r["n_pts"]
     per_rank = gather_ranks(world, {"rank": rank, "device": local, "walls_s": r["walls_s_rank"],
                                     "pcg_branches": r["pcg_branches"]})
@@ -896,6 +939,7 @@ def cfg5_main(args, world, rank, local, dist_info):
         "config": {"workload": r["workload"], "baseline_config": cfg["name"], "n_img": n_img,
                    "k": k, "n_pts": n_pts,
                    "parallelism": f"pair-sharded dp{world} + point-sharded BA"},
+        "full": bool(args.full),
         "distributed": dict(dist_info, per_rank=per_rank),
         "cfg5": r,
     }
@@ -965,6 +1009,40 @@ def graph_checksum(torch, graph):
     v = (g[:, 0] * 1000003 + g[:, 1] * 1009 + g[:, 2]) % P
     w = torch.arange(1, g.shape[0] + 1, device=g.device, dtype=torch.int64) % P
     return int(((v * w) % P).sum().item() % P)
+
+
+DUMP_MAX_ROWS = 4_000_000   # graph rows kept by --dump-outputs: 3 float32 each, 48 MB
+DUMP_SEED = 0
+
+
+def graph_outputs(torch, graph, n_pairs):
+    """--dump-outputs of a match + verify step: the verified graph rows [n,3] (pair, queryIdx,
+    trainIdx; every value < 2^24, exact in float32) or, past DUMP_MAX_ROWS, the rows at
+    DUMP_MAX_ROWS sorted indices drawn with replacement by a generator seeded DUMP_SEED (a function
+    of n alone), plus two arrays that cover the whole graph: the verified matches of every pair
+    and [row count, graph_checksum]."""
+    import numpy as np
+    n = int(graph.shape[0])
+    rows = graph
+    if n > DUMP_MAX_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_ROWS))
+        rows = graph[torch.from_numpy(idx).to(graph.device)]
+    per_pair = torch.bincount(graph[:, 0].long(), minlength=n_pairs)
+    return {"graph_rows": rows.cpu().numpy().astype(np.float32),
+            "inliers_per_pair": per_pair.cpu().numpy().astype(np.float32),
+            "graph_summary": np.array([n, graph_checksum(torch, graph)], np.float64)}
+
+
+def dump_outputs(dirname, arrays):
+    """Writes each array as dirname/<name>.npy (float32 / float64 only, <= 64 MB in all)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    log(f"bench.py: wrote {sorted(arrays)} ({total} bytes) to {dirname}")
 
 
 def ransac_flops(stats, n_hyp, steps):

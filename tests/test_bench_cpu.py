@@ -86,6 +86,33 @@ def test_visible_gpus_from_kfd_topology(tmp_path):
     assert set(sel) == {"torch_imported", "hip_runtime_mapped"}
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: a graph past DUMP_MAX_ROWS is written as a seeded sample of its rows (the
+    same rows for the same graph size) beside the per-pair counts and the checksum of the whole
+    graph; the files are float32 / float64 and stay under 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, n_pairs = bench.DUMP_MAX_ROWS + 12345, 1000
+    g = torch.stack([torch.arange(n) * n_pairs // n, torch.arange(n) % 4096,
+                     (torch.arange(n) * 7) % 4096], 1).int()
+    a, b = bench.graph_outputs(torch, g, n_pairs), bench.graph_outputs(torch, g.clone(), n_pairs)
+    assert a["graph_rows"].shape == (bench.DUMP_MAX_ROWS, 3)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert (np.diff(a["graph_rows"][:, 0]) >= 0).all()          # rows kept in graph order
+    assert a["inliers_per_pair"].sum() == n
+    assert a["graph_summary"].tolist() == [float(n), float(bench.graph_checksum(torch, g))]
+    small = bench.graph_outputs(torch, g[:50], n_pairs)
+    assert np.array_equal(small["graph_rows"], g[:50].numpy().astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "o"), a)
+    files = sorted((tmp_path / "o").iterdir())
+    assert [f.name for f in files] == ["graph_rows.npy", "graph_summary.npy",
+                                       "inliers_per_pair.npy"]
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    assert all(np.load(f).dtype in (np.float32, np.float64) for f in files)
+
+
 def test_launcher_never_imports_torch(tmp_path):
     """The self-launcher refuses a too-large --gpus before any rank starts, and its selfcheck
     says torch was never imported into it (run with a fake 1-GPU topology)."""

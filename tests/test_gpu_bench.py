@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_json_contract():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg3", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline"]
+           "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -130,7 +130,7 @@ def test_bench_cfg4_line_carries_cfg5_at_two_ranks():
     scenes: the N = 2 line's cfg5 reconstruction equals N = 1's bit for bit (points, registered
     views, median and mean reprojection error), and its BAs ran sharded."""
     base = ["--config", "cfg4", "--n-img", "12", "--k", "512", "--n-hyp", "1024", "--steps", "1",
-            "--warmup", "1", "--no-cpu-baseline", "--no-fp64", "--no-cfg3", "--no-local",
+            "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fp64", "--no-cfg3", "--no-local",
             "--cfg5-n-img", "16", "--cfg5-k", "1024"]
     one = _bench(base)
     assert one.returncode == 0, one.stderr[-3000:]
@@ -166,7 +166,7 @@ def test_bench_cfg5_line_and_two_rank_rehearsal():
     rehearsal through the self-launcher (matching sharded, BA sharded, each PCG branch) returns
     the single-process reconstruction."""
     base = ["--config", "cfg5", "--n-img", "12", "--k", "1024", "--steps", "1", "--warmup", "1"]
-    one = _bench(base)
+    one = _bench(base + ["--full"])
     assert one.returncode == 0, one.stderr[-3000:]
     d1 = json.loads([l for l in one.stdout.splitlines() if l.strip()][-1])
     c1 = d1["cfg5"]
@@ -198,7 +198,8 @@ def test_bench_cfg4_local_leg():
     """the N = 1 cfg4 line carries `cfg4_local`, the same step on the cfg5
     local-visibility scene (most pairs fail verification, as in a real capture); small shape."""
     out = _bench(["--config", "cfg4", "--n-img", "24", "--k", "1024", "--steps", "1",
-                  "--warmup", "1", "--no-cpu-baseline", "--no-cfg3", "--no-cfg5", "--no-fp64"])
+                  "--warmup", "1", "--full", "--no-cpu-baseline", "--no-cfg3", "--no-cfg5",
+                  "--no-fp64"])
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
     loc = d["cfg4_local"]
@@ -208,3 +209,39 @@ def test_bench_cfg4_local_leg():
     assert abs(loc["value"] - loc["verified_matches_per_step"] * 1e3 / loc["ms_per_step"]) \
         <= 1e-6 * loc["value"]
     assert 0 < loc["k2_executed_frac"] <= 1.0 and loc["match_ms"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line without the --full figures; --dump-outputs writes the
+    last timed step's graph as float32 / float64 .npy files that agree with the line, and a second
+    run with the same arguments writes the same arrays."""
+    import numpy as np
+    args = ["--config", "cfg3", "--gpus", "1", "--steps", "2", "--warmup", "1"]
+    outs = []
+    for name in ("a", "b"):
+        out = _bench(args + ["--dump-outputs", str(tmp_path / name)])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+    d = outs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["full"] is False and d["steps"] == 2 and d["ms_per_step"] > 0
+    for k in ("roofline", "calib", "step_roofline", "k2_fp64", "cpu_baseline", "cfg1_cpu", "cfg2",
+              "cfg3", "cfg4_local", "cfg5"):
+        assert k not in d, k
+    assert d["verified_matches_per_step"] == 554009
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["graph_rows.npy", "graph_summary.npy", "inliers_per_pair.npy"]
+    arr = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert sum(a.nbytes for a in arr.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in arr.values())
+    assert arr["graph_rows.npy"].shape == (554009, 3)
+    assert arr["inliers_per_pair.npy"].shape == (1225,)
+    assert arr["inliers_per_pair.npy"].sum() == 554009
+    assert arr["graph_summary.npy"].tolist() == [554009.0, float(d["graph_checksum"])]
+    rows = arr["graph_rows.npy"].astype(np.int64)
+    assert (np.bincount(rows[:, 0], minlength=1225) == arr["inliers_per_pair.npy"]).all()
+    for f in files:
+        assert np.array_equal(arr[f], np.load(tmp_path / "b" / f)), f
