@@ -422,6 +422,14 @@ int sfm_orb_batch(sfm_ctx* ctx, const uint8_t* images, int32_t n_img, int32_t H,
  * in-kernel clock (GHz), fraction of the nominal dense-i8 peak.  Synchronises the stream. */
 int sfm_calib_mfma_i8(sfm_ctx* ctx, float target_ms, double* out);
 
+/* ---- measurement: the mutual certificate of the L2 ratio path -----------------------------------
+ * Counters of sfm_match_batch's L2 mutual + ratio rule on the forward-scan path (DESIGN.md §4.1
+ * "certificate"), default off.  enable != 0: every later such call on ctx first clears, then
+ * fills three device counters (a few atomics per pair).  out != NULL: synchronises the stream and
+ * writes the LAST call's (pairs the certificate decided, pairs it flagged for the reverse scan,
+ * exact dot products it took).  Off: the kernels take no counter pointer at all. */
+int sfm_match_cert_stats(sfm_ctx* ctx, int32_t enable, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

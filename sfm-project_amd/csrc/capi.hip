@@ -87,6 +87,7 @@ int sfm_ctx_destroy(sfm_ctx* ctx) {
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->poll_ev) (void)hipEventDestroy(ctx->poll_ev);
     if (ctx->rs_acc) (void)hipFree(ctx->rs_acc);
+    if (ctx->cert_acc) (void)hipFree(ctx->cert_acc);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return SFM_OK;

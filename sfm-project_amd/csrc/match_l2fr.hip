@@ -22,11 +22,16 @@
 //     exactly; if e1 > e2 the unique train with e == e1 is the nearest neighbour j1 and d1 is
 //     exact; the ratio test is decided exactly unless d2's unit ambiguity straddles it; ties
 //     (e1 == e2) and straddles take an exact full-row scan (rare);
-//   * reverse scan (mutual only): the same MFMA scan with the survivors' j1 rows as queries and
-//     the other image streamed: top-2 of e'(j1, q') = x'_q'.y'_j1 - ceil(|x'_q'|^2 / 2) over q';
-//     q is j1's nearest query iff e'(j1, q) == E1 > E2 (E1 == E2 == e'(j1, q): exact column scan).
-// MFMA work: 1 + (survivor fraction) of the fused kernel; VALU per element: 1.5 instructions of
-// the top-2 network instead of about 4.5 + the transposes.
+//   * certificate (mutual only, l2fr_mutual_cert_kernel): the cross check of a pair's survivors
+//     decided from the forward records' bounds, an owner table over the trains and exact dot
+//     products for the few (threat, survivor) pairs the bounds leave open; a pair with too many
+//     of those is flagged for the reverse scan (on descriptor data: none);
+//   * reverse scan (mutual only, flagged pairs): the same MFMA scan with the survivors' j1 rows
+//     as queries and the other image streamed: top-2 of e'(j1, q') = x'_q'.y'_j1 -
+//     ceil(|x'_q'|^2 / 2) over q'; q is j1's nearest query iff e'(j1, q) == E1 > E2
+//     (E1 == E2 == e'(j1, q): exact column scan).
+// MFMA work: 1 (+ the survivor fraction of a flagged pair) of the fused kernel; VALU per element:
+// 1.5 instructions of the top-2 network instead of about 4.5 + the transposes.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -851,7 +856,7 @@ __global__ __launch_bounds__(256) void l2fr_recover_kernel(
                 else if (sfm::ratio_ok(d1, d2lo, rnum, rden, true)) st = ST_PASS;
                 else if (!sfm::ratio_ok(d1, d2hi, rnum, rden, true)) st = ST_DROP;
                 else st = ST_SLOW;
-                qs[q] = make_int4(st, j, (int)d1, 0);
+                qs[q] = make_int4(st, j, (int)d1, 1);  // .w = 1: (j1, d1) exact
             }
         }
         __syncthreads();
@@ -1068,7 +1073,7 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
                     else if (sfm::ratio_ok(d1, d2lo, rnum, rden, true)) st = ST_PASS;
                     else if (!sfm::ratio_ok(d1, d2hi, rnum, rden, true)) st = ST_DROP;
                     else st = ST_SLOW;
-                    qs[qq[k]] = make_int4(st, tg * 32 + jg, (int)d1, 0);
+                    qs[qq[k]] = make_int4(st, tg * 32 + jg, (int)d1, 1);  // .w = 1: (j1, d1) exact
                 }
             }
         }
@@ -1077,11 +1082,13 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
 
 // Exact full-row scans for the SLOW queries (ties in e, straddled ratio decisions: rare), then the
 // ordered compaction of the survivors (q, j1, d1, 0) into surv[p][0..scount[p]-1] (block of 256
-// per pair).
+// per pair).  A query resolved by a row scan gets its exact record back into qst as
+// (status, j1, d1, 1), whatever its ratio verdict: after this kernel qst[p][q].w == 1 marks every
+// query whose (j1, d1) is exact (the mutual certificate's "known" queries).
 __global__ __launch_bounds__(256) void l2fr_compact_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
-    const int4* __restrict__ qst, int rnum, int rden, long long max_dist,
+    int4* __restrict__ qst, int rnum, int rden, long long max_dist,
     int4* __restrict__ surv, int32_t* __restrict__ scount, int32_t* __restrict__ out_count,
     int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
     __shared__ Top2 red[256];
@@ -1102,7 +1109,7 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
         }
         return;
     }
-    const int4* qs = qst + (size_t)p * k_pad;
+    int4* qs = qst + (size_t)p * k_pad;
     const int32_t* na_norm = norm + (size_t)a * k_pad;
     const int32_t* nb_norm = norm + (size_t)b * k_pad;
     const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
@@ -1123,7 +1130,8 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
             if (tid == who) {
                 bool keep = sfm::ratio_ok(e.b1, e.b2, rnum, rden, true);
                 keep = keep && (max_dist < 0 || e.b1 < max_dist);
-                r = make_int4(keep ? ST_PASS : ST_DROP, e.j1, (int)e.b1, 0);
+                r = make_int4(keep ? ST_PASS : ST_DROP, e.j1, (int)e.b1, 1);
+                if (!direct) qs[qq] = r;
             }
         }
         const bool keep = r.x == ST_PASS;
@@ -1138,14 +1146,174 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
     }
 }
 
-// Mutual decision from the reverse scan + ordered output (block of 256 per pair).
+// Mutual certificate (block of 256 per pair, after the compaction): decides the cross check of the
+// pair's survivors from what the forward scan already holds, in place of the reverse scan + final
+// kernel (DESIGN.md §4.1 "certificate").
+//
+// Survivor (q, j, d1) — j its lowest-index nearest train, d1 exact — is a mutual match iff no
+// query q' != q has (d(q', j), q') < (d1, q) lexicographically.  Per query q' (A' = |x'_q'|^2,
+// forward record (e1', e2'), d = A' - 2e - (|y'|^2 mod 2)):
+//   * known q' (qst.w == 1: exact (j1', d1') from the recovery or a row scan): d(q', j1') = d1',
+//     and every other train has e <= e2' (e2' the multiset second), so d(q', j) >= L2' =
+//     A' - 2 e2' - 1 (+inf when e2' is no real element);
+//   * unknown q' (dropped by the scan's interval test): every train has d(q', j) >= L1' =
+//     A' - 2 e1' - 1.
+// So (1) an owner table over the trains takes min (d1' << 32 | q') over the known queries at
+// their j1': the survivor must own j; (2) with T = max d1 over the survivors, only a "threat" — a
+// query whose bound (L2' resp. L1') is <= T — can beat a survivor at a train that is not its own
+// j1', and only a survivor with d1 >= that bound: those (threat, survivor) pairs get one exact
+// dot product each.  On ratio-test survivors of descriptor data there are none (survivor d1 is far
+// below everybody's second distance: that is what passing the test means).
+// A pair whose threats x survivors exceed `cap` (or whose threats do not fit the list) is flagged
+// instead: flag[p] = 1, rcount[p] = scount[p], and the reverse scan + final kernel decide it.
+// Every other pair gets rcount[p] = 0 (its reverse-scan blocks exit at once) and its output here,
+// in the final kernel's order.  stats (nullptr: off): pairs certified, pairs flagged, exact dots.
+constexpr int CERT_TMAX = 2048;  // threat list entries (LDS)
+// Default cap on threats x survivors of one pair.  One unit is a list walk step (an LDS read, a
+// 16-byte survivor read, a compare) and at most one exact 128-byte dot product with two dependent
+// global row reads: the pair's block walks 256 units at a time.  Measured (profiles/r07/README.md,
+// tests/perf/k1_cert_cap.py: every query a survivor and a threat): a block walks a unit in 2.4 ns
+// with 21 % of the units taking their dot product, so at most 11.6 ns per unit if all did.  The
+// reverse scan + final kernel cost a pair 0.82 us of the whole GPU at K = 4096 (cfg4 shard) and
+// 0.19 us at K = 2048 (cfg3), i.e. 630 / 147 us of one of the 768 certificate blocks resident at
+// a time (3 per CU): break-even at 54 K / 12.7 K units when every unit takes its dot product,
+// five times that at the measured mix.  16384 sits at the low end of that band.
+// Override: SFM_L2FR_CERT_CAP (0: every pair takes the fallback).
+constexpr long long CERT_CAP_DEFAULT = 16384;
+
+__global__ __launch_bounds__(256) void l2fr_mutual_cert_kernel(
+    const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
+    const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
+    const int4* __restrict__ fwd, const int4* __restrict__ qst, const int4* __restrict__ surv,
+    const int32_t* __restrict__ scount, long long cap, int32_t* __restrict__ rcount,
+    uint8_t* __restrict__ flag, unsigned long long* __restrict__ stats,
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
+    int32_t* __restrict__ out_dist) {
+    __shared__ unsigned long long owner[KMAX];
+    __shared__ int tbound[CERT_TMAX];
+    __shared__ unsigned short tq[CERT_TMAX];
+    __shared__ unsigned char killed[KMAX];
+    __shared__ int wmax[4], wsum[8];
+    __shared__ int nthreat;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int a = pairs[2 * p], b = pairs[2 * p + 1];
+    const int na = n_kp[a], nb = n_kp[b];
+    const int S = (na > 0 && nb > 0) ? scount[p] : 0;
+    if (cap <= 0) {  // every pair through the reverse scan
+        if (tid == 0) {
+            rcount[p] = S;
+            flag[p] = 1;
+            if (stats) atomicAdd(&stats[1], 1ull);
+        }
+        return;
+    }
+    if (S == 0) {  // nothing to decide
+        if (tid == 0) {
+            rcount[p] = 0;
+            flag[p] = 0;
+            out_count[p] = 0;
+            if (stats) atomicAdd(&stats[0], 1ull);
+        }
+        return;
+    }
+    const int4* fw = fwd + (size_t)p * k_pad;
+    const int4* qs = qst + (size_t)p * k_pad;
+    const int4* sv = surv + (size_t)p * k_pad;
+    const int32_t* na_norm = norm + (size_t)a * k_pad;
+    const int32_t* nb_norm = norm + (size_t)b * k_pad;
+    const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
+    const uint4* dbv = (const uint4*)(desc + (size_t)b * k_max * D);
+
+    // T = max d1 over the survivors; the tables start empty
+    int tmax = 0;
+    for (int k = tid; k < S; k += 256) {
+        tmax = max(tmax, sv[k].z);
+        killed[k] = 0;
+    }
+    for (int j = tid; j < nb; j += 256) owner[j] = ~0ull;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) tmax = max(tmax, __shfl_xor(tmax, m));
+    if ((tid & 63) == 0) wmax[tid >> 6] = tmax;
+    if (tid == 0) nthreat = 0;
+    __syncthreads();
+    const long long T = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+
+    // owner table and threat list over all queries of image a
+    for (int q = tid; q < na; q += 256) {
+        const int4 r = qs[q];
+        const int4 f = fw[q];
+        const long long A = na_norm[q];
+        long long bound;
+        if (r.w == 1) {
+            if ((unsigned)r.y < (unsigned)nb)
+                atomicMin(&owner[r.y], ((unsigned long long)(unsigned)r.z << 32) | (unsigned)q);
+            bound = f.y > E_VALID ? A - 2LL * f.y - 1 : sfm::DIST_INF;
+        } else {
+            bound = A - 2LL * f.x - 1;
+        }
+        if (bound <= T) {
+            const int i = atomicAdd(&nthreat, 1);
+            if (i < CERT_TMAX) {
+                tq[i] = (unsigned short)q;
+                tbound[i] = (int)bound;
+            }
+        }
+    }
+    __syncthreads();
+    const int nT = nthreat;
+    if (nT > CERT_TMAX || (long long)nT * S > cap) {  // block-uniform: the fallback decides
+        if (tid == 0) {
+            rcount[p] = S;
+            flag[p] = 1;
+            if (stats) atomicAdd(&stats[1], 1ull);
+        }
+        return;
+    }
+    // threats against survivors: exact distances where the bound does not already decide
+    unsigned dots = 0;
+    for (int i = tid; i < nT * S; i += 256) {
+        const int t = i / S, k = i - t * S;
+        const int4 s = sv[k];
+        const int qp = tq[t];
+        if (qp == s.x || s.z < tbound[t]) continue;
+        const int dot = dot128(qa + (size_t)qp * SLOTS, dbv + (size_t)s.y * SLOTS);
+        const long long d = (long long)na_norm[qp] + nb_norm[s.y] - 2LL * dot;
+        if (d < s.z || (d == s.z && qp < s.x)) killed[k] = 1;
+        ++dots;
+    }
+    if (stats && dots) atomicAdd(&stats[2], (unsigned long long)dots);
+    __syncthreads();
+    int32_t* om = out_match + (size_t)p * k_max * 2;
+    int32_t* od = out_dist + (size_t)p * k_max;
+    int base = 0;
+    for (int k0 = 0; k0 < S; k0 += 256) {
+        const int k = k0 + tid;
+        int4 s = make_int4(0, 0, 0, 0);
+        bool keep = false;
+        if (k < S) {
+            s = sv[k];
+            keep = !killed[k] &&
+                   owner[s.y] == (((unsigned long long)(unsigned)s.z << 32) | (unsigned)s.x);
+        }
+        base = sfm::compact256(keep, s.x, s.y, s.z, base, wsum, om, od);
+    }
+    if (tid == 0) {
+        out_count[p] = base;
+        rcount[p] = 0;
+        flag[p] = 0;
+        if (stats) atomicAdd(&stats[0], 1ull);
+    }
+}
+
+// Mutual decision from the reverse scan + ordered output (block of 256 per pair).  flag != nullptr
+// (the certificate ran): only the pairs it flagged; the others have their output already.
 __global__ __launch_bounds__(256) void l2fr_final_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ cinit,
     const int32_t* __restrict__ pairs, const int4* __restrict__ surv,
     const int32_t* __restrict__ scount, const int4* __restrict__ rev, int mutual,
-    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
-    int32_t* __restrict__ out_dist) {
+    const uint8_t* __restrict__ flag, int32_t* __restrict__ out_count,
+    int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
     __shared__ int wsum[8];
     __shared__ int amb[256];
     __shared__ int namb;
@@ -1153,6 +1321,7 @@ __global__ __launch_bounds__(256) void l2fr_final_kernel(
     __shared__ long long redd[256];
     __shared__ int redq[256];
     const int p = blockIdx.x, tid = threadIdx.x;
+    if (flag && !flag[p]) return;  // block-uniform
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
     const int na = n_kp[a], nb = n_kp[b];
     const int S = (na > 0 && nb > 0) ? scount[p] : 0;
@@ -1262,8 +1431,12 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     const size_t rinfob = sizeof(int4) * (size_t)n_rng_max * REC_R;
     const size_t sinfob = sfm::align_up(sizeof(int4) * (size_t)n_pairs, 256);
     const size_t uinfob = sfm::align_up(UNIT * sizeof(int4) * (size_t)n_pairs, 256);
+    const size_t flagb = sfm::align_up((size_t)n_pairs, 256);
+    // cfg4 in one launch (124 750 pairs x 4096): the three record tables 24.5 GB, cls 0.5 GB, the
+    // certificate's counts and flags 0.6 MB, everything else under 0.3 GB
     char* ws = (char*)sfm::workspace(ctx, 256 + 2 * tab + 3 * recb + cntb + descb + 2 * ordb + clsb +
-                                              256 + rngb + rinfob + 256 + sinfob + uinfob + 256);
+                                              256 + rngb + rinfob + 256 + sinfob + uinfob + 256 +
+                                              cntb + flagb);
     if (!ws) return SFM_ERR_NOMEM;
     char* w = ws;
     uint8_t* zero_row = (uint8_t*)w; w += 256;
@@ -1283,6 +1456,8 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     int4* sinfo_f = (int4*)sfm::align_up((size_t)w, 256);
     int4* uinfo = (int4*)((char*)sinfo_f + sinfob);
     int32_t* n_units = (int32_t*)((char*)uinfo + uinfob);
+    int32_t* rcount = (int32_t*)((char*)n_units + 256);  // reverse-scan survivor counts (certificate)
+    uint8_t* flag = (uint8_t*)rcount + cntb;              // pairs the certificate left to the fallback
     // the forward scan by units of two pairs sharing their query image (build_units;
     // SFM_L2FR_UNITS=0: one pair per block, XCD-contiguous runs by train image)
     static const bool units_env = [] {
@@ -1338,7 +1513,7 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     // the ratio rule alone: the compaction writes the output itself (no final kernel)
     const bool direct = !mutual && dmode == 0;
     hipLaunchKernelGGL(l2fr_compact_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, norm, pairs, (const int4*)qst, prm->ratio_num, prm->ratio_den,
+                       k_pad, norm, pairs, qst, prm->ratio_num, prm->ratio_den,
                        (long long)prm->max_dist, surv, scount, direct ? out_count : nullptr,
                        out_match, out_dist);
     SFM_HIP_CHECK(hipGetLastError());
@@ -1349,11 +1524,29 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
                            out_dist);
         return SFM_OK;
     }
+    // mutual rule: the certificate decides every pair it can from the forward records (it reads
+    // qst before the reverse scan overwrites the aliased rev); the reverse scan and the final
+    // kernel then see only the flagged pairs (rcount = 0 / flag = 0 elsewhere: their blocks exit
+    // at once).  SFM_L2FR_CERT=0: no certificate, every pair through the reverse scan.
+    const char* ce = getenv("SFM_L2FR_CERT");
+    const bool cert = mutual && dmode == 0 && !(ce && ce[0] == '0');
+    if (cert) {
+        const char* cc = getenv("SFM_L2FR_CERT_CAP");
+        const long long cap = cc ? atoll(cc) : CERT_CAP_DEFAULT;
+        unsigned long long* stats = ctx->cert_stats ? ctx->cert_acc : nullptr;
+        if (stats)  // the counters are the last call's
+            SFM_HIP_CHECK(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(l2fr_mutual_cert_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp,
+                           k_max, k_pad, norm, pairs, (const int4*)fwd, (const int4*)qst,
+                           (const int4*)surv, (const int32_t*)scount, cap, rcount, flag, stats,
+                           out_count, out_match, out_dist);
+        SFM_HIP_CHECK(hipGetLastError());
+    }
     if (mutual) {
         hipLaunchKernelGGL(l2fr_scan_kernel<true>, dim3(grid), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp,
                            k_max, k_pad, cinit, zero_row, pairs, n_qblk, sord_r,
                            (const int4*)nullptr, n_blk,
-                           (const int4*)surv, (const int32_t*)scount, rev, fc,
+                           (const int4*)surv, (const int32_t*)(cert ? rcount : scount), rev, fc,
                            (const int32_t*)nullptr);
         SFM_HIP_CHECK(hipGetLastError());
     }
@@ -1364,9 +1557,27 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
         return SFM_OK;
     }
     hipLaunchKernelGGL(l2fr_final_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, norm, cinit, pairs, surv, scount, rev, mutual ? 1 : 0, out_count,
-                       out_match, out_dist);
+                       k_pad, norm, cinit, pairs, surv, scount, rev, mutual ? 1 : 0,
+                       (const uint8_t*)(cert ? flag : nullptr), out_count, out_match, out_dist);
     SFM_HIP_CHECK(hipGetLastError());
+    return SFM_OK;
+}
+
+// Totals of the last mutual + ratio call through the certificate (sfmcore.h).
+extern "C" int sfm_match_cert_stats(sfm_ctx* ctx, int32_t enable, uint64_t* out) {
+    SFM_REQUIRE(ctx, "sfm_match_cert_stats: ctx is NULL");
+    SFM_HIP_CHECK(hipSetDevice(ctx->device));
+    if (!ctx->cert_acc) {
+        SFM_HIP_CHECK(hipMalloc(&ctx->cert_acc, 3 * sizeof(unsigned long long)));
+        SFM_HIP_CHECK(hipMemsetAsync(ctx->cert_acc, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    }
+    if (out) {  // synchronises the context's stream
+        unsigned long long h[3];
+        SFM_HIP_CHECK(hipMemcpyAsync(h, ctx->cert_acc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+        SFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
+    }
+    ctx->cert_stats = enable ? 1 : 0;
     return SFM_OK;
 }
 

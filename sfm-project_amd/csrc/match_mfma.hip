@@ -1506,9 +1506,12 @@ int sfm_match_l2_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, 
                         int32_t k_max, const int32_t* pairs, int32_t n_pairs,
                         const sfm_match_params* prm, int32_t* out_count, int32_t* out_match,
                         int32_t* out_dist) {
-    // Path per rule (cfg3, 1225 pairs x 2048): mutual or OpenCV cross check ->
-    // the value-only-row / column-only kernel; ratio test without cross check -> the forward/
-    // reverse path (match_l2fr.hip); no cross check and no ratio -> the fused key kernel.
+    // Path per rule: mutual + ratio test with 1536 < k_max <= 4096 -> the forward
+    // scan path with the mutual certificate (match_l2fr.hip; A/B against the mutual kernel in
+    // profiles/r07: -22 % at 1792, 2048 and 4096, inside the noise margin at 1280 and 1536, even
+    // at 1024, +51 % at 512, where its 1024-query blocks run half empty); mutual otherwise or
+    // the OpenCV cross check -> the value-only-row / column-only kernel; ratio test without
+    // cross check -> the forward scan path; no cross check and no ratio -> the fused key kernel.
     // SFM_L2_PATH=mutual|fr|fused overrides where the rule allows it.
     const char* pe = getenv("SFM_L2_PATH");
     const bool ratio = prm->ratio_den > 0;
@@ -1516,6 +1519,10 @@ int sfm_match_l2_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, 
         return mfma_match_launch(ctx, SFM_METRIC_L2, desc, n_kp, n_img, k_max, pairs, n_pairs, prm,
                                  out_count, out_match, out_dist);
     if (pe && strcmp(pe, "fr") == 0 && ratio && prm->cross_check != SFM_XC_OPENCV)
+        return sfm_match_l2fr_launch(ctx, desc, n_kp, n_img, k_max, pairs, n_pairs, prm,
+                                     out_count, out_match, out_dist);
+    if (prm->cross_check == SFM_XC_MUTUAL && ratio && k_max > 1536 && k_max <= 4096 &&
+        !(pe && strcmp(pe, "mutual") == 0))
         return sfm_match_l2fr_launch(ctx, desc, n_kp, n_img, k_max, pairs, n_pairs, prm,
                                      out_count, out_match, out_dist);
     if (prm->cross_check != SFM_XC_NONE)

@@ -23,6 +23,10 @@ struct sfm_ctx {
     // the last counted batch's per-wave counts (sfm_ransac_wave_stops): where, and its shape
     const uint32_t* rs_last_w = nullptr;
     int rs_last_pairs = 0, rs_last_hyp = 0;
+    // mutual-certificate counters (sfm_match_cert_stats): on/off and the last call's (pairs
+    // certified, pairs flagged, exact dot products)
+    int cert_stats = 0;
+    unsigned long long* cert_acc = nullptr;
     // BA chunk mode (sfm_ba_set_chunks): local chunk point offsets; n_total 0 = whole problem
     int ba_nchunk = 0, ba_ntotal = 0;
     int32_t ba_chunk_pt[17] = {0}, ba_chunk_obs[17] = {0};

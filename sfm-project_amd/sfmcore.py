@@ -27,7 +27,8 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_ba_fix_params", "sfm_orb_batch", "sfm_ransac_counts", "sfm_ba_solve_stage",
             "sfm_ransac_stats", "sfm_ransac_f_batch_f64", "sfm_graph_rows_packed",
             "sfm_graph_expand", "sfm_match_batch_both", "sfm_ransac_wave_stops",
-            "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8"]
+            "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
+            "sfm_match_cert_stats"]
 
 
 class SfmCoreError(RuntimeError):
@@ -102,6 +103,7 @@ def load_library(path: str = LIB_PATH):
                                         C.POINTER(RansacParams), vp, vp, vp, vp]
         L.sfm_ransac_stats.argtypes = [vp, i32, vp]
         L.sfm_ransac_wave_stops.argtypes = [vp, i32, i32, vp]
+        L.sfm_match_cert_stats.argtypes = [vp, i32, vp]
         L.sfm_calib_mfma_i8.argtypes = [vp, C.c_float, vp]
         L.sfm_ba_jtj.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, f64, vp,
                                  vp, vp, vp, vp, vp, vp]
@@ -320,6 +322,17 @@ class Context:
         out = (C.c_uint64 * 3)()
         self._bind_stream()
         _check(self.lib.sfm_ransac_stats(self.handle, 1 if enable else 0, out if read else None))
+        return (int(out[0]), int(out[1]), int(out[2])) if read else None
+
+    def match_cert_stats(self, enable=True, read=False):
+        """sfm_match_cert_stats: enable / disable the mutual certificate's counters (L2 mutual +
+        ratio through the forward-scan path); with read, returns the last such call's (pairs
+        certified, pairs flagged for the reverse scan, exact dot products) — synchronises the
+        stream."""
+        out = (C.c_uint64 * 3)()
+        self._bind_stream()
+        _check(self.lib.sfm_match_cert_stats(self.handle, 1 if enable else 0,
+                                             out if read else None))
         return (int(out[0]), int(out[1]), int(out[2])) if read else None
 
     def ransac_wave_stops(self, n_pairs, n_hyp):
