@@ -151,6 +151,47 @@ int sfm_ransac_stats(sfm_ctx* ctx, int32_t enable, uint64_t* out);
  * Synchronises the stream.  executed = Σ_{M>=8} n_hyp·min(128, M) + 64·Σ_w out[p][w] + M. */
 int sfm_ransac_wave_stops(sfm_ctx* ctx, int32_t n_pairs, int32_t n_hyp, uint32_t* out);
 
+/* Homography RANSAC: the second model of two-view verification (papers/schoenberger2016sfm.pdf
+ * §4.1).  An F is not identifiable on a planar scene or under pure rotation; the
+ * ratio of this count to sfm_ransac_f_batch's tells such pairs apart.  Inputs exactly as
+ * sfm_ransac_f_batch (n_hyp a multiple of 256, <= 65536); prm->thr is the FORWARD TRANSFER ERROR
+ * |H x1 - x2|^2 in squared pixels of image 2; prm->min_inliers is not read.
+ *   sampler   4 distinct matches (Floyd, as the F sampler) from ONE Philox block, key = seed,
+ *             counter = (h, 2, a, b): stream 2, disjoint from F's 0 and 1; shard-invariant
+ *   fit       null vector of the 8x9 DLT system of the 4 Hartley-normalised correspondences
+ *             (rows (x,y,1,0,0,0,-x'x,-x'y,-x') and (0,0,0,x,y,1,-y'x,-y'y,-y')), Householder QR
+ *   validity  count -1 if the QR breaks down, an entry of H is not finite, or the 4 sample points
+ *             do not share one strict sign of w = h31 x + h32 y + h33
+ *   inlier    sign(w) equals the sample's and (u - x2 w)^2 + (v - y2 w)^2 - thr s2^2 w^2 < 0 with
+ *             (u, v, w) = H (x1, y1, 1) in normalised coordinates (division-free)
+ *   winner    max count, lowest h among equal counts
+ *   out_inl_count [n_pairs] i32  best count (-1 if fewer than 4 matches; 0 if no valid hypothesis)
+ *   out_best_h    [n_pairs] i32  winning hypothesis id (-1 if fewer than 4 matches)
+ *   out_mask      [n_pairs][k_max] u8  inlier flag per tentative match; the whole row is
+ *                                   written, zero from match_count on
+ *   out_H         [n_pairs][9] f32  H in normalised coordinates, row-major, exactly as fitted
+ *                                   (zero if fewer than 4 matches or no valid hypothesis)
+ *   out_norm      [n_pairs][6] f32  as sfm_ransac_f_batch, bit-identical for >= 8 matches; the
+ *                                   same rule down to 4 matches, zero below
+ * Does not touch the sfm_ransac_stats counters.
+ */
+int sfm_ransac_h_batch(sfm_ctx* ctx, const float* kps, int32_t n_img, int32_t k_max,
+                       const int32_t* pairs, int32_t n_pairs, const int32_t* match_count,
+                       const int32_t* matches, const sfm_ransac_params* prm,
+                       int32_t* out_inl_count, int32_t* out_best_h, uint8_t* out_mask,
+                       float* out_H, float* out_norm);
+
+/* Diagnostic companion of sfm_ransac_h_batch: the count of EVERY hypothesis (no pruning),
+ * out_counts [n_pairs][n_hyp] i32 (-1: invalid hypothesis or fewer than 4 matches), by the batch's
+ * kernel with pruning off; out_norm as above.  Optional (NULL: not written): out_hyp_H
+ * [n_pairs][n_hyp][9] f32, every hypothesis's H in normalised coordinates (zero where the count
+ * is -1).
+ */
+int sfm_ransac_h_counts(sfm_ctx* ctx, const float* kps, int32_t n_img, int32_t k_max,
+                        const int32_t* pairs, int32_t n_pairs, const int32_t* match_count,
+                        const int32_t* matches, const sfm_ransac_params* prm, int32_t* out_counts,
+                        float* out_norm, float* out_hyp_H);
+
 /* ---- verified match graph -------------------------------------------------------------------
  * Replaces the pair_matches list of code/pipeline.py:42-47 (Pair(img_inx_1, img_inx_2, matches)
  * for every non-empty pair) for a batch: rows (pair_base + pair, queryIdx, trainIdx) of the RANSAC

@@ -6,6 +6,18 @@
 `n_hyp` hypotheses per pair drawn by a counter-based RNG keyed (seed, a, b, h), Sampson error in
 squared pixels below `thr`, best = max inlier count (lowest hypothesis id on ties); a pair is
 verified when the count reaches `min_inliers`.  All arithmetic runs in libsfmcore (HIP).
+
+Multi-model verification (the paper's §4.1): an F is not identifiable on a planar
+scene or under pure rotation, yet such pairs pass the F test.  `verify_pair_h` /
+`two_view_geometry` / `verify_pairs(homography=True)` also fit a homography by 4-point RANSAC
+(sfm_ransac_h_batch) on the same tentative matches and `classify_two_view` compares the two inlier
+counts.
+
+DEFAULT_H_THRESHOLD: the homography threshold is the forward transfer error |H x1 - x2|^2 in
+squared pixels of image 2.  At sigma = 0.5 px per coordinate the F path's Sampson threshold of
+1.0 px^2 keeps P(chi^2_1 < 4) = 0.954 of the true matches; the same share under the transfer error
+(2 sigma^2 chi^2_2 with noise in both images) needs about 3.1 px^2, so 4.0 px^2 is the matching,
+slightly more generous default.  DEFAULT_MAX_H_RATIO is COLMAP's max_H_inlier_ratio.
 """
 from __future__ import annotations
 
@@ -17,17 +29,97 @@ DEFAULT_HYPOTHESES = 4096
 DEFAULT_SEED = 42
 DEFAULT_THRESHOLD = 1.0   # Sampson error, px^2
 DEFAULT_MIN_INLIERS = 15  # COLMAP's default N_F
+DEFAULT_H_THRESHOLD = 4.0  # forward transfer error, px^2 of image 2 (module docstring)
+DEFAULT_MAX_H_RATIO = 0.8  # COLMAP's max_H_inlier_ratio
 
 
 def denormalize_F(Fn, norm) -> np.ndarray:
     """Pixel-space F = T2^T Fn T1 (fp64), unit Frobenius norm.  norm = (cx1,cy1,s1,cx2,cy2,s2)."""
     Fn = np.asarray(Fn, np.float64).reshape(3, 3)
-    cx1, cy1, s1, cx2, cy2, s2 = [float(v) for v in norm]
-    T1 = np.array([[s1, 0, -s1 * cx1], [0, s1, -s1 * cy1], [0, 0, 1.0]])
-    T2 = np.array([[s2, 0, -s2 * cx2], [0, s2, -s2 * cy2], [0, 0, 1.0]])
+    T1, T2 = _norm_transforms(norm)
     F = T2.T @ Fn @ T1
     n = np.linalg.norm(F)
     return F / n if n > 0 else F
+
+
+def denormalize_H(Hn, norm) -> np.ndarray:
+    """Pixel-space H = T2^-1 Hn T1 (fp64), unit Frobenius norm, sign fixed so that H[2,2] >= 0.
+    norm = (cx1,cy1,s1,cx2,cy2,s2); a zero norm (a pair below 4 matches) gives the zero matrix."""
+    Hn = np.asarray(Hn, np.float64).reshape(3, 3)
+    T1, _ = _norm_transforms(norm)
+    cx2, cy2, s2 = [float(v) for v in norm[3:6]]
+    if s2 == 0.0:
+        return np.zeros((3, 3))
+    T2inv = np.array([[1.0 / s2, 0, cx2], [0, 1.0 / s2, cy2], [0, 0, 1.0]])
+    H = T2inv @ Hn @ T1
+    n = np.linalg.norm(H)
+    H = H / n if n > 0 else H
+    return -H if H[2, 2] < 0 else H
+
+
+def _norm_transforms(norm):
+    cx1, cy1, s1, cx2, cy2, s2 = [float(v) for v in norm]
+    T1 = np.array([[s1, 0, -s1 * cx1], [0, s1, -s1 * cy1], [0, 0, 1.0]])
+    T2 = np.array([[s2, 0, -s2 * cx2], [0, s2, -s2 * cy2], [0, 0, 1.0]])
+    return T1, T2
+
+
+def classify_two_view(f_count, h_count, min_inliers=DEFAULT_MIN_INLIERS,
+                      max_h_ratio=DEFAULT_MAX_H_RATIO) -> str:
+    """Two-view configuration from the F and H inlier counts on the same tentative matches:
+    "unverified" when f_count < min_inliers; "planar_or_panoramic" when h_count >= min_inliers and
+    h_count / f_count > max_h_ratio (the F is then not trustworthy: a planar scene or a pure
+    rotation); "general" otherwise."""
+    f_count, h_count = int(f_count), int(h_count)
+    if f_count < min_inliers:
+        return "unverified"
+    if h_count >= min_inliers and _h_ratio(f_count, h_count) > max_h_ratio:
+        return "planar_or_panoramic"
+    return "general"
+
+
+def _h_ratio(f_count, h_count) -> float:
+    return max(int(h_count), 0) / int(f_count) if int(f_count) > 0 else 0.0
+
+
+def _upload_pair(kp1, kp2, matches, pair, device):
+    """One pair as a 1-pair batch on the device: (ctx, kps, pairs, count, match, M).  The RNG is
+    keyed by the pair's image ids, so they are passed through."""
+    import torch
+    mt = _match_array(matches)
+    k1, k2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
+    k_max = max(len(k1), len(k2), len(mt), 1)
+    match = np.zeros((1, k_max, 2), np.int32)
+    match[0, :len(mt)] = mt
+    dev = torch.device("cuda", device)
+    ctx = sfmcore.context(device)
+    a, b = int(pair[0]), int(pair[1])
+    n_img = max(a, b) + 1
+    kps_full = np.zeros((n_img, k_max, 2), np.float32)
+    kps_full[a, :len(k1)] = k1
+    kps_full[b, :len(k2)] = k2
+    # one int32 upload (pair, match count, 61 pad, matches)
+    head = np.zeros(64, np.int32)
+    head[:3] = (a, b, len(mt))
+    up = torch.from_numpy(np.concatenate([head, match.reshape(-1)])).to(dev)
+    return (ctx, torch.from_numpy(kps_full).to(dev), up[:2].view(1, 2), up[2:3],
+            up[64:].view(1, k_max, 2), len(mt))
+
+
+def _pack(out, model, M):
+    """The first pair's results of a batch as one byte tensor: count, best_h, model, norm, mask."""
+    import torch
+    u8 = lambda t: t.reshape(-1).view(torch.uint8)
+    return torch.cat([u8(out["inl_count"][:1]), u8(out["best_h"][:1]), u8(out[model][0]),
+                      u8(out["norm"][0]), out["mask"][0, :M]])
+
+
+def _unpack(back, M):
+    cnt = int(back[0:4].view(np.int32)[0])
+    best_h = int(back[4:8].view(np.int32)[0])
+    model = back[8:44].view(np.float32).copy()
+    norm = back[44:68].view(np.float32).copy()
+    return cnt, best_h, model, norm, back[68:68 + M].astype(bool)
 
 
 def verify_pair(kp1, kp2, matches, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT_SEED,
@@ -36,40 +128,48 @@ def verify_pair(kp1, kp2, matches, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES, seed=D
 
     Returns dict(F [3,3] pixel F, inliers [n] match indices (ascending), count, verified,
     best_h)."""
-    import torch
-    mt = _match_array(matches)
-    k1, k2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
-    k_max = max(len(k1), len(k2), len(mt), 1)
-    kps = np.zeros((2, k_max, 2), np.float32)
-    kps[0, :len(k1)] = k1
-    kps[1, :len(k2)] = k2
-    match = np.zeros((1, k_max, 2), np.int32)
-    match[0, :len(mt)] = mt
-    dev = torch.device("cuda", device)
-    ctx = sfmcore.context(device)
-    # the RNG is keyed by the pair's image ids; pass them through as a 1-pair batch
-    a, b = int(pair[0]), int(pair[1])
-    n_img = max(a, b) + 1
-    kps_full = np.zeros((n_img, k_max, 2), np.float32)
-    kps_full[a] = kps[0]
-    kps_full[b] = kps[1]
-    # one int32 upload (pair, match count, 61 pad, matches) and one byte download of the results
-    head = np.zeros(64, np.int32)
-    head[:3] = (a, b, len(mt))
-    up = torch.from_numpy(np.concatenate([head, match.reshape(-1)])).to(dev)
-    out = ctx.ransac_batch(torch.from_numpy(kps_full).to(dev), up[:2].view(1, 2), up[2:3],
-                           up[64:].view(1, k_max, 2), n_hyp=n_hyp, seed=seed, thr=thr,
+    ctx, kps, pr, count, match, M = _upload_pair(kp1, kp2, matches, pair, device)
+    out = ctx.ransac_batch(kps, pr, count, match, n_hyp=n_hyp, seed=seed, thr=thr,
                            min_inliers=min_inliers)
-    M = len(mt)
-    u8 = lambda t: t.reshape(-1).view(torch.uint8)
-    back = torch.cat([u8(out["inl_count"][:1]), u8(out["best_h"][:1]), u8(out["F"][0]),
-                      u8(out["norm"][0]), out["mask"][0, :M]]).cpu().numpy()
-    cnt = int(back[0:4].view(np.int32)[0])
-    best_h = int(back[4:8].view(np.int32)[0])
-    F = denormalize_F(back[8:44].view(np.float32).copy(), back[44:68].view(np.float32).copy())
-    mask = back[68:68 + M].astype(bool)
-    return dict(F=F, inliers=np.nonzero(mask)[0], count=max(cnt, 0),
+    # one byte download of the results
+    cnt, best_h, Fn, norm, mask = _unpack(_pack(out, "F", M).cpu().numpy(), M)
+    return dict(F=denormalize_F(Fn, norm), inliers=np.nonzero(mask)[0], count=max(cnt, 0),
                 verified=cnt >= min_inliers, best_h=best_h)
+
+
+def verify_pair_h(kp1, kp2, matches, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT_SEED,
+                  thr=DEFAULT_H_THRESHOLD, min_inliers=DEFAULT_MIN_INLIERS, device=0):
+    """The homography mirror of verify_pair (4-point RANSAC, forward transfer error below `thr`
+    px^2 in image 2).  Returns dict(H [3,3] pixel H (unit norm, H[2,2] >= 0), inliers [n] match
+    indices (ascending), count, verified, best_h)."""
+    ctx, kps, pr, count, match, M = _upload_pair(kp1, kp2, matches, pair, device)
+    out = ctx.ransac_h_batch(kps, pr, count, match, n_hyp=n_hyp, seed=seed, thr=thr,
+                             min_inliers=min_inliers)
+    cnt, best_h, Hn, norm, mask = _unpack(_pack(out, "H", M).cpu().numpy(), M)
+    return dict(H=denormalize_H(Hn, norm), inliers=np.nonzero(mask)[0], count=max(cnt, 0),
+                verified=cnt >= min_inliers, best_h=best_h)
+
+
+def two_view_geometry(kp1, kp2, matches, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES,
+                      seed=DEFAULT_SEED, thr=DEFAULT_THRESHOLD, h_thr=DEFAULT_H_THRESHOLD,
+                      min_inliers=DEFAULT_MIN_INLIERS, max_h_ratio=DEFAULT_MAX_H_RATIO, device=0):
+    """F and H RANSAC on the same tentative matches (one upload, the two batch calls, one
+    download) and the configuration classify_two_view gives their counts.  Returns dict(config,
+    F, H (pixel space), f_inliers, h_inliers (match indices), f_count, h_count, h_ratio)."""
+    import torch
+    ctx, kps, pr, count, match, M = _upload_pair(kp1, kp2, matches, pair, device)
+    of = ctx.ransac_batch(kps, pr, count, match, n_hyp=n_hyp, seed=seed, thr=thr,
+                          min_inliers=min_inliers)
+    oh = ctx.ransac_h_batch(kps, pr, count, match, n_hyp=n_hyp, seed=seed, thr=h_thr,
+                            min_inliers=min_inliers)
+    back = torch.cat([_pack(of, "F", M), _pack(oh, "H", M)]).cpu().numpy()
+    fc, _, Fn, fnorm, fmask = _unpack(back[:68 + M], M)
+    hc, _, Hn, hnorm, hmask = _unpack(back[68 + M:], M)
+    fc, hc = max(fc, 0), max(hc, 0)
+    return dict(config=classify_two_view(fc, hc, min_inliers, max_h_ratio),
+                F=denormalize_F(Fn, fnorm), H=denormalize_H(Hn, hnorm),
+                f_inliers=np.nonzero(fmask)[0], h_inliers=np.nonzero(hmask)[0],
+                f_count=fc, h_count=hc, h_ratio=_h_ratio(fc, hc))
 
 
 def _match_array(matches) -> np.ndarray:
@@ -80,14 +180,20 @@ def _match_array(matches) -> np.ndarray:
 
 def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT_SEED,
                  thr=DEFAULT_THRESHOLD, min_inliers=DEFAULT_MIN_INLIERS, device=0,
-                 chunk=8192):
+                 chunk=8192, homography=False, h_thr=DEFAULT_H_THRESHOLD,
+                 max_h_ratio=DEFAULT_MAX_H_RATIO):
     """Verifies the reference's pair list (code/pipeline.py:36-47: Pair objects with img_inx_1,
     img_inx_2, matches; the ordered N(N-1) enumeration or any subset) in batched calls of at most
     `chunk` pairs (host and device buffers are [chunk, k_max] — constant memory however long the
     list): keypoints[i] = [K_i,2] pixel coordinates of image i.  Returns the verified
     subset (input order) with `.matches` reduced to the inliers (ascending match index) and `.F`
     (pixel F, unit norm) attached.  Results equal verify_pair on each pair (the RNG is keyed by the
-    pair's image ids, so they depend neither on the batch nor on the chunking)."""
+    pair's image ids, so they depend neither on the batch nor on the chunking).
+
+    homography=True: the H batch (threshold `h_thr`) runs per chunk next to the F batch on the same
+    tentative matches, and every verified pair also gets `.H` (pixel H), `.h_count`, `.h_ratio` and
+    `.config` (classify_two_view with `max_h_ratio`), equal to two_view_geometry on that pair.  The
+    verified subset and `.matches` stay the F result."""
     import torch
     chunk = int(chunk)
     if chunk < 1:   # ADVICE r4: a non-positive chunk used to return no verified pair, silently
@@ -114,10 +220,16 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
             m = _match_array(pr.matches)
             match[p, :len(m)] = m
         cc = counts[c0:c0 + P]
-        out = ctx.ransac_batch(kps_d, torch.from_numpy(np.ascontiguousarray(pairs[c0:c0 + P])).to(dev),
-                               torch.from_numpy(np.ascontiguousarray(cc)).to(dev),
-                               torch.from_numpy(match).to(dev), n_hyp=n_hyp, seed=seed, thr=thr,
+        pairs_d = torch.from_numpy(np.ascontiguousarray(pairs[c0:c0 + P])).to(dev)
+        cc_d = torch.from_numpy(np.ascontiguousarray(cc)).to(dev)
+        match_d = torch.from_numpy(match).to(dev)
+        out = ctx.ransac_batch(kps_d, pairs_d, cc_d, match_d, n_hyp=n_hyp, seed=seed, thr=thr,
                                min_inliers=min_inliers)
+        if homography:
+            oh = ctx.ransac_h_batch(kps_d, pairs_d, cc_d, match_d, n_hyp=n_hyp, seed=seed,
+                                    thr=h_thr, min_inliers=min_inliers)
+            hcnt = oh["inl_count"].cpu().numpy()
+            Hn, hnrm = oh["H"].cpu().numpy(), oh["norm"].cpu().numpy()
         cnt = out["inl_count"].cpu().numpy()
         mask = out["mask"].cpu().numpy()
         Fn, nrm = out["F"].cpu().numpy(), out["norm"].cpu().numpy()
@@ -126,5 +238,11 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
                 keep = np.nonzero(mask[p, :cc[p]])[0]
                 pr.matches = [pr.matches[i] for i in keep]
                 pr.F = denormalize_F(Fn[p], nrm[p])
+                if homography:
+                    hc = max(int(hcnt[p]), 0)
+                    pr.H = denormalize_H(Hn[p], hnrm[p])
+                    pr.h_count = hc
+                    pr.h_ratio = _h_ratio(cnt[p], hc)
+                    pr.config = classify_two_view(cnt[p], hc, min_inliers, max_h_ratio)
                 verified.append(pr)
     return verified

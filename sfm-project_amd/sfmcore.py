@@ -28,7 +28,7 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_ransac_stats", "sfm_ransac_f_batch_f64", "sfm_graph_rows_packed",
             "sfm_graph_expand", "sfm_match_batch_both", "sfm_ransac_wave_stops",
             "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
-            "sfm_match_cert_stats"]
+            "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts"]
 
 
 class SfmCoreError(RuntimeError):
@@ -101,6 +101,9 @@ def load_library(path: str = LIB_PATH):
         L.sfm_ransac_f_batch_f64.argtypes = L.sfm_ransac_f_batch.argtypes
         L.sfm_ransac_counts.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp,
                                         C.POINTER(RansacParams), vp, vp, vp, vp]
+        L.sfm_ransac_h_batch.argtypes = L.sfm_ransac_f_batch.argtypes
+        L.sfm_ransac_h_counts.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp,
+                                          C.POINTER(RansacParams), vp, vp, vp]
         L.sfm_ransac_stats.argtypes = [vp, i32, vp]
         L.sfm_ransac_wave_stops.argtypes = [vp, i32, i32, vp]
         L.sfm_match_cert_stats.argtypes = [vp, i32, vp]
@@ -314,6 +317,55 @@ class Context:
                                           _ptr(norm), _ptr(F) if hyp_F else None,
                                           _ptr(mk) if hyp_mask else None))
         return (counts, norm, F, mk) if (hyp_F or hyp_mask) else (counts, norm)
+
+    def ransac_h_batch(self, kps, pairs, count, match, n_hyp=4096, seed=42, thr=4.0,
+                       min_inliers=15, out=None):
+        """Homography RANSAC (sfm_ransac_h_batch) on the inputs of ransac_batch; thr is the
+        forward transfer error in squared pixels of image 2.  Returns dict of device tensors:
+        inl_count [P] (-1: fewer than 4 matches), best_h [P], mask [P,k_max] u8, H [P,9] f32
+        (normalised coordinates, row-major), norm [P,6] (bit-identical to ransac_batch's)."""
+        torch = self.torch
+        n_img, k_max, _ = kps.shape
+        P = pairs.shape[0]
+        dev = kps.device
+        if kps.dtype != torch.float32 or not kps.is_contiguous():
+            raise SfmCoreError("ransac_h_batch: kps must be contiguous float32")
+        if out is None:
+            out = dict(inl_count=torch.empty(P, dtype=torch.int32, device=dev),
+                       best_h=torch.empty(P, dtype=torch.int32, device=dev),
+                       mask=torch.empty((P, k_max), dtype=torch.uint8, device=dev),
+                       H=torch.empty((P, 9), dtype=torch.float32, device=dev),
+                       norm=torch.empty((P, 6), dtype=torch.float32, device=dev))
+        prm = RansacParams(int(n_hyp), int(min_inliers), float(thr), 0, int(seed))
+        self._bind_stream()
+        _check(self.lib.sfm_ransac_h_batch(self.handle, _ptr(kps), n_img, k_max, _ptr(pairs), P,
+                                           _ptr(count), _ptr(match), C.byref(prm),
+                                           _ptr(out["inl_count"]), _ptr(out["best_h"]),
+                                           _ptr(out["mask"]), _ptr(out["H"]), _ptr(out["norm"])))
+        return out
+
+    def ransac_h_counts(self, kps, pairs, count, match, n_hyp=4096, seed=42, thr=4.0,
+                        hyp_H=False):
+        """Diagnostic: the count of every homography hypothesis ([P, n_hyp] i32 device tensor, -1
+        for invalid hypotheses / pairs with < 4 matches) and norm [P,6], by ransac_h_batch's
+        kernel without pruning (sfm_ransac_h_counts); with hyp_H also every hypothesis's H
+        [P, n_hyp, 9] f32 (normalised coordinates, zero where the count is -1).
+        Returns (counts, norm) or (counts, norm, H)."""
+        torch = self.torch
+        n_img, k_max, _ = kps.shape
+        P = pairs.shape[0]
+        dev = kps.device
+        if kps.dtype != torch.float32 or not kps.is_contiguous():
+            raise SfmCoreError("ransac_h_counts: kps must be contiguous float32")
+        counts = torch.empty((P, n_hyp), dtype=torch.int32, device=dev)
+        norm = torch.empty((P, 6), dtype=torch.float32, device=dev)
+        Hh = torch.empty((P, n_hyp, 9), dtype=torch.float32, device=dev) if hyp_H else None
+        prm = RansacParams(int(n_hyp), 0, float(thr), 0, int(seed))
+        self._bind_stream()
+        _check(self.lib.sfm_ransac_h_counts(self.handle, _ptr(kps), n_img, k_max, _ptr(pairs), P,
+                                            _ptr(count), _ptr(match), C.byref(prm), _ptr(counts),
+                                            _ptr(norm), _ptr(Hh) if hyp_H else None))
+        return (counts, norm, Hh) if hyp_H else (counts, norm)
 
     def ransac_stats(self, enable=True, read=False):
         """sfm_ransac_stats: enable / disable the execution counters of ransac_batch; with read,
