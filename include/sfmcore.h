@@ -192,6 +192,45 @@ int sfm_ransac_h_counts(sfm_ctx* ctx, const float* kps, int32_t n_img, int32_t k
                         const int32_t* matches, const sfm_ransac_params* prm, int32_t* out_counts,
                         float* out_norm, float* out_hyp_H);
 
+/* Two-view relative pose of verified pairs (papers/schoenberger2016sfm.pdf
+ * §4.1-4.2): linear essential fit over the F inliers, the four (R, t) decompositions, the
+ * cheirality vote and the triangulation (ray) angle.  fp64 throughout, in a fixed operation order:
+ * tests/pose_ref.c states it and the results equal it bit for bit, whatever the batch.
+ *   kps, n_img, k_max, pairs, n_pairs, match_count, matches   as sfm_ransac_f_batch (k_max <= 8192)
+ *   mask [n_pairs][k_max] u8, inl_count [n_pairs] i32         that call's outputs
+ *   intr [n_img][4] f64                                       (f, k1, cx, cy) per image
+ *   coordinates  x_d = (kp - (cx, cy)) / f, undistorted by sfm_triangulate's rule (10 fixed-point
+ *                steps of x = x_d / (1 + k1 |x|^2) from x = x_d), once per keypoint per call
+ *   fit          N = A^T A over the masked-in matches, rows (x2x x1x, x2x x1y, x2x, x2y x1x,
+ *                x2y x1y, x2y, x1x, x1y, 1), fixed-order sums; E = eigenvector of N's smallest
+ *                eigenvalue (cyclic Jacobi, lowest index among equal eigenvalues), unit norm
+ *   candidates   from the eigenvectors of E^T E: 0 (U W V^T, +u3), 1 (U W V^T, -u3),
+ *                2 (U W^T V^T, +u3), 3 (U W^T V^T, -u3); x2 ~ R x1 + t, |t| = 1
+ *   cheirality   n_front[c] = inliers with both depths > 0 under candidate c (division-free);
+ *                best = the largest, lowest c on ties
+ *   ray angle    per inlier in front under best, between R (x1, 1) and (x2, 1): key = sin^2 up to
+ *                90 degrees, 2 - sin^2 above (monotone in the angle), rounded to f32
+ *   out_E [n_pairs][9], out_R [n_pairs][9] f64 row-major, out_t [n_pairs][3] f64
+ *   out_stat [n_pairs][8] i32 = {status, best, n_front[0..3], n_wide, inliers used}: n_wide = keys
+ *                above prm->wide_key; status 0 ok, 1 inl_count < max(prm->min_inliers, 8),
+ *                2 degenerate (a vanishing norm while building U); every other output of the pair
+ *                is zero unless status is 0
+ *   out_median_key [n_pairs] f32  lower median (index (n - 1) / 2 ascending) of those keys
+ * On a planar scene or under pure rotation the linear fit's t is not meaningful (under pure
+ * rotation R and the near-zero angle are). */
+typedef struct sfm_two_view_pose_params {
+    int32_t struct_size; /* sizeof(sfm_two_view_pose_params) of the caller: later fields can be
+                            added without reading past an older caller's struct */
+    int32_t min_inliers;
+    float wide_key;      /* sin^2 of the angle a "wide" ray pair must exceed, >= 0 */
+} sfm_two_view_pose_params;
+int sfm_two_view_pose_batch(sfm_ctx* ctx, const float* kps, int32_t n_img, int32_t k_max,
+                            const int32_t* pairs, int32_t n_pairs, const int32_t* match_count,
+                            const int32_t* matches, const uint8_t* mask,
+                            const int32_t* inl_count, const double* intr,
+                            const sfm_two_view_pose_params* prm, double* out_E, double* out_R,
+                            double* out_t, int32_t* out_stat, float* out_median_key);
+
 /* ---- verified match graph -------------------------------------------------------------------
  * Replaces the pair_matches list of code/pipeline.py:42-47 (Pair(img_inx_1, img_inx_2, matches)
  * for every non-empty pair) for a batch: rows (pair_base + pair, queryIdx, trainIdx) of the RANSAC

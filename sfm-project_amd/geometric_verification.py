@@ -13,6 +13,11 @@ scene or under pure rotation, yet such pairs pass the F test.  `verify_pair_h` /
 (sfm_ransac_h_batch) on the same tentative matches and `classify_two_view` compares the two inlier
 counts.
 
+Relative pose (the paper's §4.1-4.2): `two_view_pose` and
+`verify_pairs(poses=True, intrinsics=...)` run the pose batch (sfm_two_view_pose_batch) on the F
+inliers: a linear essential fit, its winning (R, t) by the cheirality vote, the number of inliers
+in front of both cameras and their triangulation angle (`key_to_degrees`).
+
 DEFAULT_H_THRESHOLD: the homography threshold is the forward transfer error |H x1 - x2|^2 in
 squared pixels of image 2.  At sigma = 0.5 px per coordinate the F path's Sampson threshold of
 1.0 px^2 keeps P(chi^2_1 < 4) = 0.954 of the true matches; the same share under the transfer error
@@ -31,6 +36,7 @@ DEFAULT_THRESHOLD = 1.0   # Sampson error, px^2
 DEFAULT_MIN_INLIERS = 15  # COLMAP's default N_F
 DEFAULT_H_THRESHOLD = 4.0  # forward transfer error, px^2 of image 2 (module docstring)
 DEFAULT_MAX_H_RATIO = 0.8  # COLMAP's max_H_inlier_ratio
+DEFAULT_MIN_ANGLE_DEG = 2.0  # a "wide" ray pair of the pose batch (n_wide)
 
 
 def denormalize_F(Fn, norm) -> np.ndarray:
@@ -82,9 +88,21 @@ def _h_ratio(f_count, h_count) -> float:
     return max(int(h_count), 0) / int(f_count) if int(f_count) > 0 else 0.0
 
 
-def _upload_pair(kp1, kp2, matches, pair, device):
+def key_to_degrees(key):
+    """Ray angle in degrees of a pose-batch key (sfm_two_view_pose_batch: sin^2 of the angle up to
+    90 degrees, 2 - sin^2 above; monotone over [0, 180])."""
+    k = np.asarray(key, np.float64)
+    lo = np.degrees(np.arcsin(np.sqrt(np.clip(k, 0.0, 1.0))))
+    hi = 180.0 - np.degrees(np.arcsin(np.sqrt(np.clip(2.0 - k, 0.0, 1.0))))
+    out = np.where(k <= 1.0, lo, hi)
+    return float(out) if out.ndim == 0 else out
+
+
+def _upload_pair(kp1, kp2, matches, pair, device, intr=None):
     """One pair as a 1-pair batch on the device: (ctx, kps, pairs, count, match, M).  The RNG is
-    keyed by the pair's image ids, so they are passed through."""
+    keyed by the pair's image ids, so they are passed through.  intr = (intr1, intr2): the
+    per-image (f, k1, cx, cy) ride at the end of the int32 upload and come back as a seventh
+    item, the [n_img, 4] f64 table."""
     import torch
     mt = _match_array(matches)
     k1, k2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
@@ -101,9 +119,18 @@ def _upload_pair(kp1, kp2, matches, pair, device):
     # one int32 upload (pair, match count, 61 pad, matches)
     head = np.zeros(64, np.int32)
     head[:3] = (a, b, len(mt))
-    up = torch.from_numpy(np.concatenate([head, match.reshape(-1)])).to(dev)
-    return (ctx, torch.from_numpy(kps_full).to(dev), up[:2].view(1, 2), up[2:3],
-            up[64:].view(1, k_max, 2), len(mt))
+    parts = [head, match.reshape(-1)]
+    if intr is not None:
+        it = np.ones((n_img, 4), np.float64)   # f = 1 for the images that are not in the pair
+        it[a], it[b] = np.asarray(intr[0], np.float64), np.asarray(intr[1], np.float64)
+        parts.append(it.reshape(-1).view(np.int32))
+    up = torch.from_numpy(np.concatenate(parts)).to(dev)
+    n_mt = 64 + 2 * k_max    # even: the f64 view of the tail is aligned
+    res = (ctx, torch.from_numpy(kps_full).to(dev), up[:2].view(1, 2), up[2:3],
+           up[64:n_mt].view(1, k_max, 2), len(mt))
+    if intr is not None:
+        res += (up[n_mt:].view(torch.float64).view(n_img, 4),)
+    return res
 
 
 def _pack(out, model, M):
@@ -172,6 +199,64 @@ def two_view_geometry(kp1, kp2, matches, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES,
                 f_count=fc, h_count=hc, h_ratio=_h_ratio(fc, hc))
 
 
+def _pack_pose(po, p=0):
+    """Pair p's pose-batch results as one byte tensor: E, R, t (21 f64), stat (8 i32), key (f32)."""
+    import torch
+    u8 = lambda t: t.reshape(-1).view(torch.uint8)
+    return torch.cat([u8(po["E"][p]), u8(po["R"][p]), u8(po["t"][p]), u8(po["stat"][p]),
+                      u8(po["median_key"][p:p + 1])])
+
+
+_POSE_BYTES = 21 * 8 + 8 * 4 + 4
+
+
+def _pose_fields(E, R, t, stat, key) -> dict:
+    """The public pose fields from one pair's batch outputs (zero matrices unless status is 0)."""
+    stat = [int(v) for v in stat]
+    return dict(R=np.array(R, np.float64).reshape(3, 3), t=np.array(t, np.float64),
+                E=np.array(E, np.float64).reshape(3, 3), n_front=stat[2 + stat[1]],
+                n_front_all=stat[2:6], best=stat[1], tri_angle_deg=key_to_degrees(float(key)),
+                n_wide=stat[6], status=stat[0])
+
+
+def _unpack_pose(back) -> dict:
+    f = back[:168].copy().view(np.float64)
+    stat = back[168:200].copy().view(np.int32)
+    key = back[200:204].copy().view(np.float32)[0]
+    return _pose_fields(f[:9], f[9:18], f[18:21], stat, key)
+
+
+def two_view_pose(kp1, kp2, matches, intr1, intr2, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES,
+                  seed=DEFAULT_SEED, thr=DEFAULT_THRESHOLD, min_inliers=DEFAULT_MIN_INLIERS,
+                  min_angle_deg=DEFAULT_MIN_ANGLE_DEG, device=0):
+    """F RANSAC and the relative pose of its inliers (one upload, the F batch and the pose batch
+    sfm_two_view_pose_batch, one download).  intr1 / intr2 = (f, k1, cx, cy) of the two images.
+
+    Returns verify_pair's fields (F, inliers, count, verified, best_h) and R [3,3], t [3] (unit;
+    x2 ~ R x1 + t in normalised coordinates), E [3,3] (the linear fit, unit norm), n_front (the
+    inliers in front of both cameras under the winning decomposition; n_front_all the four
+    candidates' counts, best the winner's index), tri_angle_deg (the median triangulation angle of
+    those inliers), n_wide (how many exceed min_angle_deg) and status (0 ok, 1 fewer than
+    max(min_inliers, 8) inliers, 2 degenerate; the pose fields are zero unless 0).
+
+    The fit is linear: on a planar scene it does not recover the pose, and under pure rotation
+    there is no t to recover.  Where two_view_geometry reports "planar_or_panoramic", only R and
+    the angle are meaningful (R and a near-zero angle under pure rotation)."""
+    import torch
+    ctx, kps, pr, count, match, M, intr = _upload_pair(kp1, kp2, matches, pair, device,
+                                                        intr=(intr1, intr2))
+    of = ctx.ransac_batch(kps, pr, count, match, n_hyp=n_hyp, seed=seed, thr=thr,
+                          min_inliers=min_inliers)
+    po = ctx.two_view_pose_batch(kps, intr, pr, count, match, of["mask"], of["inl_count"],
+                                 min_inliers=min_inliers, min_angle_deg=min_angle_deg)
+    back = torch.cat([_pack(of, "F", M), _pack_pose(po)]).cpu().numpy()
+    cnt, best_h, Fn, norm, mask = _unpack(back[:68 + M], M)
+    res = dict(F=denormalize_F(Fn, norm), inliers=np.nonzero(mask)[0], count=max(cnt, 0),
+               verified=cnt >= min_inliers, best_h=best_h)
+    res.update(_unpack_pose(back[68 + M:68 + M + _POSE_BYTES]))
+    return res
+
+
 def _match_array(matches) -> np.ndarray:
     if len(matches) and hasattr(matches[0], "queryIdx"):
         return np.array([[m.queryIdx, m.trainIdx] for m in matches], np.int32).reshape(-1, 2)
@@ -181,7 +266,8 @@ def _match_array(matches) -> np.ndarray:
 def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT_SEED,
                  thr=DEFAULT_THRESHOLD, min_inliers=DEFAULT_MIN_INLIERS, device=0,
                  chunk=8192, homography=False, h_thr=DEFAULT_H_THRESHOLD,
-                 max_h_ratio=DEFAULT_MAX_H_RATIO):
+                 max_h_ratio=DEFAULT_MAX_H_RATIO, poses=False, intrinsics=None,
+                 min_angle_deg=DEFAULT_MIN_ANGLE_DEG):
     """Verifies the reference's pair list (code/pipeline.py:36-47: Pair objects with img_inx_1,
     img_inx_2, matches; the ordered N(N-1) enumeration or any subset) in batched calls of at most
     `chunk` pairs (host and device buffers are [chunk, k_max] — constant memory however long the
@@ -193,9 +279,18 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
     homography=True: the H batch (threshold `h_thr`) runs per chunk next to the F batch on the same
     tentative matches, and every verified pair also gets `.H` (pixel H), `.h_count`, `.h_ratio` and
     `.config` (classify_two_view with `max_h_ratio`), equal to two_view_geometry on that pair.  The
-    verified subset and `.matches` stay the F result."""
+    verified subset and `.matches` stay the F result.
+
+    poses=True (with intrinsics[i] = (f, k1, cx, cy) of image i): the pose batch
+    (sfm_two_view_pose_batch) runs per chunk on the F batch's masks, and every verified pair also
+    gets `.R`, `.t`, `.n_front`, `.tri_angle_deg`, `.n_wide` and `.pose_status`, equal to
+    two_view_pose on that pair.  Composes with homography=True; under `.config ==
+    "planar_or_panoramic"` only `.R` and the angle are meaningful (a planar scene defeats the
+    linear essential fit, and a pure rotation has no t)."""
     import torch
     chunk = int(chunk)
+    if poses and intrinsics is None:
+        raise ValueError("verify_pairs: poses=True needs intrinsics")
     if chunk < 1:   # ADVICE r4: a non-positive chunk used to return no verified pair, silently
         raise ValueError(f"verify_pairs: chunk must be >= 1, got {chunk}")
     if not pair_matches:
@@ -211,6 +306,9 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
     dev = torch.device("cuda", device)
     ctx = sfmcore.context(device)
     kps_d = torch.from_numpy(kps).to(dev)
+    if poses:
+        intr_d = torch.from_numpy(np.ascontiguousarray(
+            np.asarray(intrinsics, np.float64)[:n_img].reshape(n_img, 4))).to(dev)
     verified = []
     for c0 in range(0, len(pair_matches), chunk):
         prs = pair_matches[c0:c0 + chunk]
@@ -230,6 +328,11 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
                                     thr=h_thr, min_inliers=min_inliers)
             hcnt = oh["inl_count"].cpu().numpy()
             Hn, hnrm = oh["H"].cpu().numpy(), oh["norm"].cpu().numpy()
+        if poses:
+            po = ctx.two_view_pose_batch(kps_d, intr_d, pairs_d, cc_d, match_d, out["mask"],
+                                         out["inl_count"], min_inliers=min_inliers,
+                                         min_angle_deg=min_angle_deg)
+            po = {k: v.cpu().numpy() for k, v in po.items()}
         cnt = out["inl_count"].cpu().numpy()
         mask = out["mask"].cpu().numpy()
         Fn, nrm = out["F"].cpu().numpy(), out["norm"].cpu().numpy()
@@ -244,5 +347,11 @@ def verify_pairs(pair_matches, keypoints, n_hyp=DEFAULT_HYPOTHESES, seed=DEFAULT
                     pr.h_count = hc
                     pr.h_ratio = _h_ratio(cnt[p], hc)
                     pr.config = classify_two_view(cnt[p], hc, min_inliers, max_h_ratio)
+                if poses:
+                    f = _pose_fields(po["E"][p], po["R"][p], po["t"][p], po["stat"][p],
+                                     po["median_key"][p])
+                    pr.R, pr.t, pr.n_front = f["R"], f["t"], f["n_front"]
+                    pr.tri_angle_deg, pr.n_wide = f["tri_angle_deg"], f["n_wide"]
+                    pr.pose_status = f["status"]
                 verified.append(pr)
     return verified

@@ -6,8 +6,10 @@ Every per-element stage runs on the GPU through the C-ABI: all-pairs matching (K
 verified-graph rows, tracks (`sfm_tracks`), triangulation (`sfm_triangulate`), batched next-view
 registration (`sfm_register_batch`, P3P RANSAC + refinement) and Levenberg-Marquardt bundle
 adjustment (`sfm_ba_jtj` / `sfm_ba_solve`).  The host does the orchestration: which images and
-tracks enter the model, and the one 3x3 essential-matrix decomposition of the initial pair (an
-8-point fit on that pair's inliers, O(1) work with no GPU counterpart).
+tracks enter the model.  The initial pair's essential-matrix fit and decomposition run on the host
+by default (`relative_pose`: an 8-point fit on that pair's inliers and four triangulations per
+candidate pair); `reconstruct(init_pair="pose")` uses their GPU counterpart instead, the batched
+`sfm_two_view_pose_batch`, and ranks the candidate pairs by their triangulation angles.
 
 Cameras: angle-axis, t, f, k1 with known intrinsics (f, k1, principal point) per image.
 """
@@ -221,7 +223,8 @@ def point_mean(err, first):
 
 def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max_err=4.0,
                 ba_iter=20, loss_s=2.0, device=0, log=None, group=None, shard_ba=False,
-                ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6):
+                ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6, init_pair="inliers",
+                init_candidates=64):
     """desc [n_img,K,D] u8, kps [n_img,K,2] pixels, n_kp [n_img], intr [n_img,4] = (f, k1, cx, cy).
     Returns a Reconstruction (cams [n_img,8], registered mask, points per track, track arrays).
     With torch.distributed initialised (one process per GPU, `group` or the default group) the
@@ -238,9 +241,17 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     auto | sharded | replicated); rec.ba_log records the branch each one took.
     ba_ftol: an LM run stops once an accepted step lowers the cost by <= ba_ftol * cost (Ceres'
     and COLMAP's function tolerance, 1e-6); at 1e-12 every bundle adjustment of the 500-image
-    cfg5 scene ran its 20 steps."""
+    cfg5 scene ran its 20 steps.
+    init_pair: how the initial pair is chosen.  "inliers" (the default): the ten pairs with the
+    most verified inliers in turn, each under the host's four essential-matrix decompositions.
+    "pose": the `init_candidates` pairs with the most inliers go through the GPU pose batch
+    (sfm_two_view_pose_batch) and are tried by descending n_wide, the number of inliers whose
+    triangulation angle exceeds 2 degrees, each under the batch's winning pose only — on a dense
+    sequence the most-matched pairs are the narrowest ones (_initial_pair_by_pose)."""
     import time
     import torch
+    if init_pair not in ("inliers", "pose"):
+        raise ValueError(f"reconstruct: init_pair must be 'inliers' or 'pose', got {init_pair!r}")
     dev = torch.device("cuda", device)
     ctx = sfmcore.context(device)
     say = log or (lambda *a: None)
@@ -287,7 +298,10 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     # rows are pair-major in pair order: a pair's rows are one slice (no host copy of the graph)
     pair_col = rows[:, 0].contiguous()
     order = np.argsort(-inl, kind="stable")
-    for p in order[:10]:
+    if init_pair == "pose":
+        _initial_pair_by_pose(rec, ctx, gb, pairs, pairs_t, order[:int(init_candidates)], intr,
+                              n_tr, max_err, say)
+    for p in (order[:10] if init_pair == "inliers" else ()):
         a, b = (int(v) for v in pairs[p])
         pv = torch.tensor([int(p)], dtype=pair_col.dtype, device=dev)
         lo = int(torch.searchsorted(pair_col, pv).item())
@@ -365,6 +379,59 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
                 ba_pcg, ba_ftol)
         tk = lap("bundle_adjust", tk)
     return rec
+
+
+def _initial_pair_by_pose(rec, ctx, gb, pairs, pairs_t, cand, intr, n_tr, max_err, say):
+    """reconstruct(init_pair="pose"): seeds rec from the candidate pairs `cand` (indices into
+    `pairs`, most inliers first).  The candidates are matched and verified again as one small
+    batch on this device (the RNG is keyed by the image ids, so the masks are the all-pairs
+    pass's, on every rank of a distributed run), the pose batch gives each its winning (R, t) and
+    n_wide, and the candidates are tried by descending n_wide (stable): status 0, then the
+    acceptance test of the default mode under that one pose — at least 30 well-reprojected
+    triangulated tracks, at least 30 of them above 1 degree.  rec.init_candidates lists
+    dict(pair, inliers, n_wide, status) of every candidate (most inliers first) and
+    rec.init_tried the pairs tried, in order; no camera is set if none passes."""
+    import torch
+    dev = pairs_t.device
+    cand = np.asarray(cand, np.int64)
+    rec.init_tried = []
+    if len(cand) == 0:
+        return
+    sub_t = pairs_t[torch.from_numpy(cand).to(dev)].contiguous()
+    count, match, _, rs = gb.run(sub_t)
+    po = ctx.two_view_pose_batch(gb.kps, torch.from_numpy(np.ascontiguousarray(intr)).to(dev),
+                                 sub_t, count, match, rs["mask"], rs["inl_count"],
+                                 min_inliers=gb.min_inliers)
+    stat, Rs, ts = (po[k].cpu().numpy() for k in ("stat", "R", "t"))
+    inl = rs["inl_count"].cpu().numpy()
+    rec.init_candidates = [dict(pair=(int(pairs[c, 0]), int(pairs[c, 1])), inliers=int(inl[j]),
+                                n_wide=int(stat[j, 6]), status=int(stat[j, 0]))
+                           for j, c in enumerate(cand)]
+    for j in np.argsort(-stat[:, 6], kind="stable"):
+        a, b = rec.init_candidates[j]["pair"]
+        rec.init_tried.append((a, b))
+        if stat[j, 0] != 0:
+            continue
+        ta, tb = rec.obs_d[0][rec.obs_d[1] == a], rec.obs_d[0][rec.obs_d[1] == b]
+        common = torch.unique(ta[torch.isin(ta, tb)]).cpu().numpy()
+        cams = rec.cams.copy()
+        cams[a, :6] = 0.0
+        cams[b, :3] = _angle_axis(Rs[j].reshape(3, 3))
+        cams[b, 3:6] = ts[j]
+        pts, st = (t.cpu().numpy() for t in
+                   _triangulate(ctx, cams, intr, [a, b], common, rec.obs_d, n_tr))
+        good = int(np.sum((st[:, 3] == 0) & (st[:, 0] < max_err)))
+        ok = (st[:, 3] == 0) & (st[:, 0] < max_err) & (st[:, 1] > 1.0)
+        if good >= 30 and int(ok.sum()) >= 30:
+            rec.cams = cams
+            sel = torch.from_numpy(common[ok]).to(dev)
+            rec.pts_d[sel] = torch.from_numpy(np.ascontiguousarray(pts[ok])).to(dev)
+            rec.has_d[sel] = True
+            rec.registered[[a, b]] = True
+            rec.gauge = (a, b)
+            say(f"initial pair ({a}, {b}) by pose: n_wide {int(stat[j, 6])}, "
+                f"{int(ok.sum())} points")
+            return
 
 
 def _triangulate(ctx, cams, intr, imgs, tracks, obs_d, n_tr):

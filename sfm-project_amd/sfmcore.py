@@ -28,7 +28,8 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_ransac_stats", "sfm_ransac_f_batch_f64", "sfm_graph_rows_packed",
             "sfm_graph_expand", "sfm_match_batch_both", "sfm_ransac_wave_stops",
             "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
-            "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts"]
+            "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
+            "sfm_two_view_pose_batch"]
 
 
 class SfmCoreError(RuntimeError):
@@ -58,6 +59,10 @@ class OrbParams(C.Structure):
 class RansacParams(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("min_inliers", C.c_int32), ("thr", C.c_float),
                 ("_pad", C.c_int32), ("seed", C.c_uint64)]
+
+
+class TwoViewPoseParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("min_inliers", C.c_int32), ("wide_key", C.c_float)]
 
 
 # stages of sfm_ba_solve_stage (include/sfmcore.h)
@@ -104,6 +109,8 @@ def load_library(path: str = LIB_PATH):
         L.sfm_ransac_h_batch.argtypes = L.sfm_ransac_f_batch.argtypes
         L.sfm_ransac_h_counts.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp,
                                           C.POINTER(RansacParams), vp, vp, vp]
+        L.sfm_two_view_pose_batch.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp,
+                                              C.POINTER(TwoViewPoseParams), vp, vp, vp, vp, vp]
         L.sfm_ransac_stats.argtypes = [vp, i32, vp]
         L.sfm_ransac_wave_stops.argtypes = [vp, i32, i32, vp]
         L.sfm_match_cert_stats.argtypes = [vp, i32, vp]
@@ -133,6 +140,11 @@ def load_library(path: str = LIB_PATH):
             getattr(L, name).restype = getattr(L, name).restype or C.c_int
         _lib = L
         return L
+
+
+def angle_key(angle_deg) -> np.float32:
+    """The f32 ray-angle key of an angle up to 90 degrees: sin^2 (two_view_pose_batch's wide_key)."""
+    return np.float32(np.sin(np.deg2rad(float(angle_deg))) ** 2)
 
 
 def _check(rc: int):
@@ -366,6 +378,46 @@ class Context:
                                             _ptr(count), _ptr(match), C.byref(prm), _ptr(counts),
                                             _ptr(norm), _ptr(Hh) if hyp_H else None))
         return (counts, norm, Hh) if hyp_H else (counts, norm)
+
+    def two_view_pose_batch(self, kps, intr, pairs, count, match, mask, inl_count,
+                            min_inliers=15, min_angle_deg=2.0, out=None):
+        """Relative pose of verified pairs (sfm_two_view_pose_batch): kps [n_img,k_max,2] f32,
+        intr [n_img,4] f64 (f, k1, cx, cy), pairs / count / match as ransac_batch, mask and
+        inl_count that call's outputs.  Returns dict of device tensors: E [P,9], R [P,9], t [P,3]
+        f64 (x2 ~ R x1 + t, |t| = 1), stat [P,8] i32 = (status, best, n_front[4], n_wide,
+        inliers used), median_key [P] f32 (key_to_degrees turns it into the median triangulation
+        angle).  n_wide counts the inliers in front whose ray angle exceeds min_angle_deg (the
+        host passes wide_key = sin^2 of it, below 90 degrees).  status 0 ok, 1 too few inliers,
+        2 degenerate; the other outputs of a pair are zero unless 0."""
+        torch = self.torch
+        _expect("two_view_pose_batch", ("kps", kps, torch.float32, (kps.shape[1], 2)),
+                ("intr", intr, torch.float64, (4,)), ("pairs", pairs, torch.int32, (2,)),
+                ("count", count, torch.int32, ()), ("match", match, torch.int32, (kps.shape[1], 2)),
+                ("mask", mask, torch.uint8, (kps.shape[1],)),
+                ("inl_count", inl_count, torch.int32, ()))
+        n_img, k_max, _ = kps.shape
+        P = pairs.shape[0]
+        if intr.shape[0] != n_img or not (count.shape[0] == match.shape[0] == mask.shape[0]
+                                          == inl_count.shape[0] == P):
+            raise SfmCoreError("two_view_pose_batch: intr must have one row per image and "
+                               "count / match / mask / inl_count one per pair")
+        if not 0.0 <= float(min_angle_deg) <= 90.0:
+            raise SfmCoreError("two_view_pose_batch: min_angle_deg must lie in [0, 90]")
+        dev = kps.device
+        if out is None:
+            out = dict(E=torch.empty((P, 9), dtype=torch.float64, device=dev),
+                       R=torch.empty((P, 9), dtype=torch.float64, device=dev),
+                       t=torch.empty((P, 3), dtype=torch.float64, device=dev),
+                       stat=torch.empty((P, 8), dtype=torch.int32, device=dev),
+                       median_key=torch.empty(P, dtype=torch.float32, device=dev))
+        prm = TwoViewPoseParams(C.sizeof(TwoViewPoseParams), int(min_inliers),
+                                float(angle_key(min_angle_deg)))
+        self._bind_stream()
+        _check(self.lib.sfm_two_view_pose_batch(
+            self.handle, _ptr(kps), n_img, k_max, _ptr(pairs), P, _ptr(count), _ptr(match),
+            _ptr(mask), _ptr(inl_count), _ptr(intr), C.byref(prm), _ptr(out["E"]), _ptr(out["R"]),
+            _ptr(out["t"]), _ptr(out["stat"]), _ptr(out["median_key"])))
+        return out
 
     def ransac_stats(self, enable=True, read=False):
         """sfm_ransac_stats: enable / disable the execution counters of ransac_batch; with read,
