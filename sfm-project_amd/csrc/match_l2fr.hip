@@ -36,6 +36,7 @@
 #include <climits>
 #include <cstdlib>
 
+#include "l2fr_records.h"
 #include "match_common.h"
 
 namespace {
@@ -70,7 +71,9 @@ constexpr int RPP = 1024 / D;                // rows per 1 KB DMA piece
 constexpr int KALIGN = CHUNK > GROUP ? CHUNK : GROUP;
 constexpr int KMAX = 4096;
 constexpr int PAD_INIT = -(1 << 30);         // accumulator init of a padded train row
-constexpr int E_VALID = -(1 << 23);          // e of a real element is > -2^22
+constexpr int E_VALID = l2fr::E_NONE;        // e of a real element is > -2^22
+static_assert(D == l2fr::REC_D && KMAX == l2fr::REC_KMAX, "l2fr_records.h is sized for D and KMAX");
+typedef unsigned long long rec8;             // a packed 8-byte record (l2fr_records.h)
 
 enum : unsigned char { ST_DROP = 0, ST_CAND = 1, ST_SLOW = 2, ST_PASS = 3 };
 
@@ -296,13 +299,13 @@ __global__ __launch_bounds__(1024) void l2fr_setup_kernel(
 
 // Ratio bounds of one forward record: DROP (cannot pass even at the favourable ends of the d1, d2
 // intervals), SLOW (e1 == e2: the nearest neighbour is not unique in e) or CAND.
-__device__ __forceinline__ unsigned char classify(int4 r, long long A, int rnum, int rden,
+__device__ __forceinline__ unsigned char classify(int e1, int e2, long long A, int rnum, int rden,
                                                   long long max_dist) {
-    const long long d1lo = max(A - 2LL * r.x - 1, 0LL);
-    const long long d2hi = r.y > E_VALID ? A - 2LL * r.y : sfm::DIST_INF;
+    const long long d1lo = max(A - 2LL * e1 - 1, 0LL);
+    const long long d2hi = e2 > E_VALID ? A - 2LL * e2 : sfm::DIST_INF;
     if (!sfm::ratio_ok(d1lo, d2hi, rnum, rden, true) || (max_dist >= 0 && !(d1lo < max_dist)))
         return ST_DROP;
-    return (r.y == r.x) ? ST_SLOW : ST_CAND;
+    return (e2 == e1) ? ST_SLOW : ST_CAND;
 }
 
 // What the forward scan needs to classify its records (unused by the reverse scan).
@@ -310,8 +313,8 @@ struct FwdCls {
     const int32_t* norm;     // [n_img][k_pad] |x'|^2
     int rnum, rden;          // ratio num/den
     long long max_dist;
-    int4* qst;               // [P][k_pad] DROP / SLOW statuses
-    uint8_t* cls;            // [P][k_pad] e1 tile of a candidate (< 128), 0xFF otherwise
+    rec8* fwd;               // [P][k_pad] packed forward records (e1, e2, tile of e1)
+    uint8_t* cls;            // [P][k_pad] e1 tile of a candidate (< 128), CLS_SLOW or CLS_DROP
 };
 
 #ifdef L2FR_CLOCK
@@ -330,7 +333,7 @@ __device__ unsigned long long g_l2fr_clock[L2FR_CLOCK_W * L2FR_CLOCK_SLOTS];
 // The MFMA scan.  Forward (REV = false): queries = image pairs[p][0] rows 0..n-1, streamed trains =
 // image pairs[p][1].  Reverse (REV = true): queries = the survivor list's j1 rows of image
 // pairs[p][1] (entries 0..qcount[p]-1), streamed = image pairs[p][0].  Output per query entry:
-// (e1, e2, tile of e1, 0) at out[p][entry].
+// reverse (e1, e2, tile of e1, 0) at out[p][entry]; forward the packed record at fc.fwd[p][entry].
 //
 // Geometry as the fused kernel (match_mfma.hip): 512-thread workgroup = 8 waves x 4 query tiles,
 // query fragments in VGPRs for the whole kernel, trains through LDS in 256-row chunks,
@@ -447,14 +450,17 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_kernel
     const uint8_t* da = desc + (size_t)qi * k_max * D;
 
     // One query's record (e1, e2, tile of e1) -> out, and the forward scan's ratio classification.
+    // Forward: the packed record at fc.fwd[p][entry] and the class byte (ratio bounds: a dropped
+    // or slow query is marked there and gets no other record, a candidate goes to the recovery).
     auto emit = [&](int e, int e1, int e2, int t) {
-        const int4 rec = make_int4(e1, e2, t, 0);
-        out[(size_t)p * k_pad + e] = rec;
-        if (!REV) {  // ratio bounds: drop / slow now, candidates go to the recovery
+        if (REV) {
+            out[(size_t)p * k_pad + e] = make_int4(e1, e2, t, 0);
+        } else {
+            fc.fwd[(size_t)p * k_pad + e] = l2fr::pack_fwd(e1, e2, t);
             const unsigned char st =
-                classify(rec, fc.norm[(size_t)qi * k_pad + e], fc.rnum, fc.rden, fc.max_dist);
-            fc.cls[(size_t)p * k_pad + e] = st == ST_CAND ? (uint8_t)t : (uint8_t)0xFF;
-            if (st != ST_CAND) fc.qst[(size_t)p * k_pad + e] = make_int4(st, 0, 0, 0);
+                classify(e1, e2, fc.norm[(size_t)qi * k_pad + e], fc.rnum, fc.rden, fc.max_dist);
+            fc.cls[(size_t)p * k_pad + e] =
+                st == ST_CAND ? (uint8_t)t : (st == ST_SLOW ? l2fr::CLS_SLOW : l2fr::CLS_DROP);
         }
     };
 
@@ -753,116 +759,6 @@ __device__ __forceinline__ int compact_rec(bool keep, int4 rec, int base, int* w
     return base + tot;
 }
 
-// Recovery (block of 256 per (pair, group of 8 train tiles)).  The group's 256 train rows (with
-// their accumulator init and |y'|^2) are staged in LDS, slot-swizzled for conflict-free
-// row-per-lane reads; the candidates of the group (cls == group, written by the forward scan) are
-// processed in batches of 64 whose query rows and records are staged too, so the only global
-// traffic is a few bulk loads per block.  Per candidate, 32 lanes (one train each) recompute the
-// tile's dot products exactly, the unique train with e == e1 is the nearest neighbour j1, and the
-// ratio test is decided exactly where d2's unit ambiguity allows: qst[p][q] = (status, j1, d1).
-__global__ __launch_bounds__(256) void l2fr_recover_kernel(
-    const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
-    const int32_t* __restrict__ norm, const int32_t* __restrict__ cinit,
-    const int32_t* __restrict__ pairs, const int4* __restrict__ fwd,
-    const uint8_t* __restrict__ cls, int rnum, int rden, long long max_dist,
-    int4* __restrict__ qst) {
-    __shared__ uint4 tiles[GROUP * SLOTS];   // 256 train rows, slot s of row r at s ^ (r & 7)
-    __shared__ int tci[GROUP], tnb[GROUP];   // their accumulator init and |y'|^2
-    __shared__ uint4 qrows[64 * SLOTS];      // a batch of 64 candidate query rows
-    __shared__ int4 crec[64];
-    __shared__ int cq[64], cA[64];
-    __shared__ short clist[KMAX];
-    __shared__ int ccount;
-    const int p = blockIdx.x, grp = blockIdx.y, tid = threadIdx.x;
-    const int a = pairs[2 * p], b = pairs[2 * p + 1];
-    const int na = n_kp[a], nb = n_kp[b];
-    const int ntiles = (nb + 31) >> 5, tg = grp * 8;
-    if (na <= 0 || nb <= 0 || tg >= ntiles) return;  // block-uniform
-    const int4* fw = fwd + (size_t)p * k_pad;
-    int4* qs = qst + (size_t)p * k_pad;
-    const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
-    const uint4* db = (const uint4*)(desc + (size_t)b * k_max * D);
-
-    // bulk loads first (one round trip): train rows, their tables, the candidate classes
-    uint4 rv[SLOTS];
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-        const int i = tid + 256 * k, j = tg * 32 + i / SLOTS;
-        rv[k] = (j < nb) ? db[(size_t)j * SLOTS + i % SLOTS] : make_uint4(0, 0, 0, 0);
-    }
-    const int tj = tg * 32 + tid;  // < k_pad: groups cover 256 rows, k_pad is a multiple of 256
-    const int ci = cinit[(size_t)b * k_pad + tj], nn = norm[(size_t)b * k_pad + tj];
-    uint4 cv = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    if (tid * 16 < na) cv = ((const uint4*)(cls + (size_t)p * k_pad))[tid];
-    if (tid == 0) ccount = 0;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-        const int i = tid + 256 * k, r = i / SLOTS, sl = i % SLOTS;
-        tiles[r * SLOTS + (sl ^ (r & 7))] = rv[k];
-    }
-    tci[tid] = ci;
-    tnb[tid] = nn;
-    __syncthreads();
-    const unsigned cw[4] = {cv.x, cv.y, cv.z, cv.w};
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int q = tid * 16 + k;
-        if (q < na && ((cw[k >> 2] >> (8 * (k & 3))) & 0xFF) >> 3 == (unsigned)grp)
-            clist[atomicAdd(&ccount, 1)] = (short)q;
-    }
-    __syncthreads();
-    const int nc = ccount;
-    const int g = tid >> 5, t = tid & 31;
-    for (int c0 = 0; c0 < nc; c0 += 64) {
-        const int nbat = min(64, nc - c0);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int i = tid + 256 * k, c = i / SLOTS;
-            if (c < nbat) qrows[i] = qa[(size_t)clist[c0 + c] * SLOTS + i % SLOTS];
-        }
-        if (tid < nbat) {
-            const int q = clist[c0 + tid];
-            cq[tid] = q;
-            crec[tid] = fw[q];
-            cA[tid] = norm[(size_t)a * k_pad + q];
-        }
-        __syncthreads();
-        for (int c = g; c < nbat; c += 8) {
-            const int q = cq[c];
-            const int4 r = crec[c];
-            const int row = (r.z - tg) * 32 + t, j = r.z * 32 + t;
-            const uint4* x = &qrows[c * SLOTS];
-            const uint4* y = &tiles[row * SLOTS];
-            int dot = 0;
-#pragma unroll
-            for (int k = 0; k < SLOTS; ++k) {
-                const uint4 u = x[k], v = y[k ^ (row & 7)];
-                dot = __builtin_amdgcn_sdot4((int)u.x, (int)v.x, dot, false);
-                dot = __builtin_amdgcn_sdot4((int)u.y, (int)v.y, dot, false);
-                dot = __builtin_amdgcn_sdot4((int)u.z, (int)v.z, dot, false);
-                dot = __builtin_amdgcn_sdot4((int)u.w, (int)v.w, dot, false);
-            }
-            const bool hit = (j < nb) && (dot + tci[row] == r.x);
-            const unsigned long long bal = __ballot(hit);
-            const unsigned m = (unsigned)(bal >> (32 * (g & 1)));
-            if (t == 0 && m == 0) qs[q] = make_int4(ST_SLOW, 0, 0, 0);  // defensive
-            if (m != 0 && t == __builtin_ctz(m)) {
-                const long long A = cA[c];
-                const long long d1 = A - (2LL * dot - tnb[row]);
-                const long long d2lo = r.y > E_VALID ? A - 2LL * r.y - 1 : sfm::DIST_INF;
-                const long long d2hi = r.y > E_VALID ? A - 2LL * r.y : sfm::DIST_INF;
-                int st;
-                if (max_dist >= 0 && !(d1 < max_dist)) st = ST_DROP;
-                else if (sfm::ratio_ok(d1, d2lo, rnum, rden, true)) st = ST_PASS;
-                else if (!sfm::ratio_ok(d1, d2hi, rnum, rden, true)) st = ST_DROP;
-                else st = ST_SLOW;
-                qs[q] = make_int4(st, j, (int)d1, 1);  // .w = 1: (j1, d1) exact
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // Recovery, MFMA form: one block of 256 (4 waves) per (range of up to REC_R pairs that share
 // their train image b, group of 8 train tiles of b).  A gather: ~1.2 M candidates at cfg2, each
 // needing its query row and one 32-train tile, so the kernel is built for few dependent round
@@ -888,15 +784,19 @@ constexpr int REC_SB = L2FR_REC_SB;  // sub-batches of 32 candidates per wave an
 __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_kernel(
     const uint8_t* __restrict__ desc, int k_max, int k_pad, const int32_t* __restrict__ norm,
     const int32_t* __restrict__ cinit, const int4* __restrict__ rinfo,
-    const int32_t* __restrict__ n_rng, const int4* __restrict__ fwd,
+    const int32_t* __restrict__ n_rng, const rec8* __restrict__ fwd,
     const uint8_t* __restrict__ cls, int rnum, int rden, long long max_dist,
-    int4* __restrict__ qst) {
+    rec8* __restrict__ qst) {
     __shared__ unsigned short clist[REC_R * KMAX];  // (pair in range) << 12 | query, by tile
     __shared__ __attribute__((aligned(16))) int gini[GROUP];
     __shared__ unsigned char gpar[GROUP];
     __shared__ unsigned long long wlo[4], whi[4];
     __shared__ int toff[9];
-    const int ri = blockIdx.x, grp = blockIdx.y, tid = threadIdx.x;
+    // group-major within a range: a range's blocks are dispatched together, so the pairs' class
+    // bytes and the lines of their forward records come from HBM once for all of them, and group
+    // g of every range lands on XCD g % 8, whose L2 keeps that group's train rows of image b
+    const int ngrp = k_pad / GROUP;
+    const int ri = (int)(blockIdx.x / ngrp), grp = (int)(blockIdx.x % ngrp), tid = threadIdx.x;
     if (ri >= *n_rng) return;  // block-uniform
     const int wave = tid >> 6, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
     int4 pi[REC_R];
@@ -1007,12 +907,12 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
     const int t0 = tg + 2 * wave;
     for (int c0 = w0; c0 < w1; c0 += 32 * REC_SB) {
         v4i bf[REC_SB][NK];
-        int4 rc[REC_SB];
-        int qq[REC_SB], pp[REC_SB], AA[REC_SB];
+        rec8 rc[REC_SB];
+        int ce[REC_SB], AA[REC_SB];   // ce: the candidate's clist entry, -1 on an idle lane
 #pragma unroll
         for (int k = 0; k < REC_SB; ++k) {
             const int c = c0 + 32 * k + r32;
-            qq[k] = -1;
+            ce[k] = -1;
             if (c < w1) {
                 const int en = clist[c], e = en >> 12, q = en & 0xFFF;
                 int p = pi[0].x, a = pi[0].y;
@@ -1026,19 +926,18 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
                 for (int s = 0; s < NK; ++s) bf[k][s] = *(const v4i*)(xr + 16 * s);
                 rc[k] = fwd[(size_t)p * k_pad + q];
                 AA[k] = norm[(size_t)a * k_pad + q];
-                qq[k] = q;
-                pp[k] = p;
+                ce[k] = en;
             } else {
 #pragma unroll
                 for (int s = 0; s < NK; ++s) bf[k][s] = v4i{0, 0, 0, 0};
-                rc[k] = make_int4(0, 0, -1, 0);
+                rc[k] = 0;   // an idle lane: nothing is written for it
             }
         }
 #pragma unroll
         for (int k = 0; k < REC_SB; ++k) {
             if (c0 + 32 * k >= w1) break;  // wave-uniform
-            const int4 r = rc[k];
-            const int mine = r.z - t0;  // 0 / 1: the candidate's tile (always one of the wave's)
+            const l2fr::Fwd r = l2fr::unpack_fwd(rc[k]);
+            const int mine = r.tile - t0;  // 0 / 1: the candidate's tile (always one of the wave's)
             int hit = -1;
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -1055,25 +954,29 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
                     acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[u][s], bf[k][s], acc, 0, 0, 0);
 #pragma unroll
                 for (int rr = 0; rr < 16; ++rr)
-                    hit = (mine == u && acc[rr] == r.x) ? 8 * (rr >> 2) + 4 * h + (rr & 3) : hit;
+                    hit = (mine == u && acc[rr] == r.e1) ? 8 * (rr >> 2) + 4 * h + (rr & 3) : hit;
             }
             hit = max(hit, __shfl_xor(hit, 32));
-            if (h == 0 && qq[k] >= 0) {
-                int4* qs = qst + (size_t)pp[k] * k_pad;
+            if (h == 0 && ce[k] >= 0) {
+                const int e = ce[k] >> 12;
+                int p = pi[0].x;
+#pragma unroll
+                for (int f = 1; f < REC_R; ++f) p = e == f ? pi[f].x : p;
+                rec8* qs = qst + (size_t)p * k_pad + (ce[k] & 0xFFF);
                 if (hit < 0) {
-                    qs[qq[k]] = make_int4(ST_SLOW, 0, 0, 0);  // defensive
+                    *qs = l2fr::pack_res(ST_SLOW, 0, 0, 0);  // defensive
                 } else {
                     const int jg = (2 * wave + mine) * 32 + hit;  // row in the group
                     const long long A = AA[k];
-                    const long long d1 = A - 2LL * r.x - gpar[jg];
-                    const long long d2lo = r.y > E_VALID ? A - 2LL * r.y - 1 : sfm::DIST_INF;
-                    const long long d2hi = r.y > E_VALID ? A - 2LL * r.y : sfm::DIST_INF;
+                    const long long d1 = A - 2LL * r.e1 - gpar[jg];
+                    const long long d2lo = r.e2 > E_VALID ? A - 2LL * r.e2 - 1 : sfm::DIST_INF;
+                    const long long d2hi = r.e2 > E_VALID ? A - 2LL * r.e2 : sfm::DIST_INF;
                     int st;
                     if (max_dist >= 0 && !(d1 < max_dist)) st = ST_DROP;
                     else if (sfm::ratio_ok(d1, d2lo, rnum, rden, true)) st = ST_PASS;
                     else if (!sfm::ratio_ok(d1, d2hi, rnum, rden, true)) st = ST_DROP;
                     else st = ST_SLOW;
-                    qs[qq[k]] = make_int4(st, tg * 32 + jg, (int)d1, 1);  // .w = 1: (j1, d1) exact
+                    *qs = l2fr::pack_res(st, tg * 32 + jg, (int)d1, 1);  // (j1, d1) exact
                 }
             }
         }
@@ -1082,18 +985,21 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
 
 // Exact full-row scans for the SLOW queries (ties in e, straddled ratio decisions: rare), then the
 // ordered compaction of the survivors (q, j1, d1, 0) into surv[p][0..scount[p]-1] (block of 256
-// per pair).  A query resolved by a row scan gets its exact record back into qst as
-// (status, j1, d1, 1), whatever its ratio verdict: after this kernel qst[p][q].w == 1 marks every
-// query whose (j1, d1) is exact (the mutual certificate's "known" queries).
+// per pair).  The class byte says what a query has: a candidate (tile) its result record from the
+// recovery, a slow one (CLS_SLOW) nothing yet, a dropped one (CLS_DROP) nothing at all.  A query
+// resolved by a row scan gets its exact record into qst as (status, j1, d1, exact = 1), whatever
+// its ratio verdict: after this kernel every query with cls != CLS_DROP has a record, and its exact
+// flag marks the queries whose (j1, d1) is exact (the mutual certificate's "known" queries).
 __global__ __launch_bounds__(256) void l2fr_compact_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
-    int4* __restrict__ qst, int rnum, int rden, long long max_dist,
-    int4* __restrict__ surv, int32_t* __restrict__ scount, int32_t* __restrict__ out_count,
-    int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
+    const uint8_t* __restrict__ cls, rec8* __restrict__ qst, int rnum, int rden, long long max_dist,
+    int4* __restrict__ surv, int32_t* __restrict__ scount, int32_t* __restrict__ smax,
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
+    int32_t* __restrict__ out_dist) {
     __shared__ Top2 red[256];
     __shared__ int slow[256];
-    __shared__ int nslow, wsum[8];
+    __shared__ int nslow, wsum[8], wmax[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
     const int na = n_kp[a], nb = n_kp[b];
@@ -1109,16 +1015,29 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
         }
         return;
     }
-    int4* qs = qst + (size_t)p * k_pad;
+    rec8* qs = qst + (size_t)p * k_pad;
+    const uint8_t* cl = cls + (size_t)p * k_pad;
     const int32_t* na_norm = norm + (size_t)a * k_pad;
     const int32_t* nb_norm = norm + (size_t)b * k_pad;
     const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
     const uint8_t* db = desc + (size_t)b * k_max * D;
     int4* sv = surv + (size_t)p * k_pad;
-    int base = 0;
+    int base = 0, dmax = 0;   // dmax: this thread's largest survivor d1
     for (int q0 = 0; q0 < na; q0 += 256) {
         const int q = q0 + tid;
-        int4 r = (q < na) ? qs[q] : make_int4(ST_DROP, 0, 0, 0);
+        int4 r = make_int4(ST_DROP, 0, 0, 0);   // (status, j1, d1, exact)
+        if (q < na) {
+            // both loads at once (no round trip for the class byte first): the result slot of a
+            // query that is no candidate holds stale bytes, read and ignored
+            const unsigned char c = cl[q];
+            const rec8 raw = qs[q];
+            if (c == l2fr::CLS_SLOW) {
+                r.x = ST_SLOW;
+            } else if (c != l2fr::CLS_DROP) {
+                const l2fr::Res u = l2fr::unpack_res(raw);
+                r = make_int4(u.st, u.j1, u.d1, u.exact);
+            }
+        }
         if (tid == 0) nslow = 0;
         __syncthreads();
         if (r.x == ST_SLOW) slow[atomicAdd(&nslow, 1)] = tid;
@@ -1131,10 +1050,11 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
                 bool keep = sfm::ratio_ok(e.b1, e.b2, rnum, rden, true);
                 keep = keep && (max_dist < 0 || e.b1 < max_dist);
                 r = make_int4(keep ? ST_PASS : ST_DROP, e.j1, (int)e.b1, 1);
-                if (!direct) qs[qq] = r;
+                if (!direct) qs[qq] = l2fr::pack_res(r.x, r.y, r.z, 1);
             }
         }
         const bool keep = r.x == ST_PASS;
+        dmax = keep ? max(dmax, r.z) : dmax;
         if (direct)
             base = sfm::compact256(keep, q, r.y, r.z, base, wsum, om, od);
         else
@@ -1144,6 +1064,13 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
         if (direct) out_count[p] = base;
         else scount[p] = base;
     }
+    if (direct) return;
+    // the largest survivor d1 (the certificate's T), so that it need not walk surv for it
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) dmax = max(dmax, __shfl_xor(dmax, m));
+    if ((tid & 63) == 0) wmax[tid >> 6] = dmax;
+    __syncthreads();
+    if (tid == 0) smax[p] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
 }
 
 // Mutual certificate (block of 256 per pair, after the compaction): decides the cross check of the
@@ -1184,8 +1111,9 @@ constexpr long long CERT_CAP_DEFAULT = 16384;
 __global__ __launch_bounds__(256) void l2fr_mutual_cert_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
-    const int4* __restrict__ fwd, const int4* __restrict__ qst, const int4* __restrict__ surv,
-    const int32_t* __restrict__ scount, long long cap, int32_t* __restrict__ rcount,
+    const rec8* __restrict__ fwd, const uint8_t* __restrict__ cls, const rec8* __restrict__ qst,
+    const int4* __restrict__ surv, const int32_t* __restrict__ scount,
+    const int32_t* __restrict__ smax, long long cap, int32_t* __restrict__ rcount,
     uint8_t* __restrict__ flag, unsigned long long* __restrict__ stats,
     int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
     int32_t* __restrict__ out_dist) {
@@ -1193,7 +1121,7 @@ __global__ __launch_bounds__(256) void l2fr_mutual_cert_kernel(
     __shared__ int tbound[CERT_TMAX];
     __shared__ unsigned short tq[CERT_TMAX];
     __shared__ unsigned char killed[KMAX];
-    __shared__ int wmax[4], wsum[8];
+    __shared__ int wsum[8];
     __shared__ int nthreat;
     const int p = blockIdx.x, tid = threadIdx.x;
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
@@ -1216,40 +1144,39 @@ __global__ __launch_bounds__(256) void l2fr_mutual_cert_kernel(
         }
         return;
     }
-    const int4* fw = fwd + (size_t)p * k_pad;
-    const int4* qs = qst + (size_t)p * k_pad;
+    const rec8* fw = fwd + (size_t)p * k_pad;
+    const rec8* qs = qst + (size_t)p * k_pad;
+    const uint8_t* cl = cls + (size_t)p * k_pad;
     const int4* sv = surv + (size_t)p * k_pad;
     const int32_t* na_norm = norm + (size_t)a * k_pad;
     const int32_t* nb_norm = norm + (size_t)b * k_pad;
     const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
     const uint4* dbv = (const uint4*)(desc + (size_t)b * k_max * D);
 
-    // T = max d1 over the survivors; the tables start empty
-    int tmax = 0;
-    for (int k = tid; k < S; k += 256) {
-        tmax = max(tmax, sv[k].z);
-        killed[k] = 0;
-    }
+    // T = max d1 over the survivors (the compaction's smax); the tables start empty
+    const long long T = smax[p];
+    for (int k = tid; k < S; k += 256) killed[k] = 0;
     for (int j = tid; j < nb; j += 256) owner[j] = ~0ull;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) tmax = max(tmax, __shfl_xor(tmax, m));
-    if ((tid & 63) == 0) wmax[tid >> 6] = tmax;
     if (tid == 0) nthreat = 0;
     __syncthreads();
-    const long long T = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
 
     // owner table and threat list over all queries of image a
     for (int q = tid; q < na; q += 256) {
-        const int4 r = qs[q];
-        const int4 f = fw[q];
+        // a dropped query has no result record (cls == CLS_DROP); every other one has (compaction)
+        // (the slot is read with the class byte, not after it: stale bytes there are ignored)
+        const unsigned char c = cl[q];
+        const rec8 raw = qs[q];
+        l2fr::Res r{ST_DROP, 0, 0, 0};
+        if (c != l2fr::CLS_DROP) r = l2fr::unpack_res(raw);
+        const l2fr::Fwd f = l2fr::unpack_fwd(fw[q]);
         const long long A = na_norm[q];
         long long bound;
-        if (r.w == 1) {
-            if ((unsigned)r.y < (unsigned)nb)
-                atomicMin(&owner[r.y], ((unsigned long long)(unsigned)r.z << 32) | (unsigned)q);
-            bound = f.y > E_VALID ? A - 2LL * f.y - 1 : sfm::DIST_INF;
+        if (r.exact == 1) {
+            if ((unsigned)r.j1 < (unsigned)nb)
+                atomicMin(&owner[r.j1], ((unsigned long long)(unsigned)r.d1 << 32) | (unsigned)q);
+            bound = f.e2 > E_VALID ? A - 2LL * f.e2 - 1 : sfm::DIST_INF;
         } else {
-            bound = A - 2LL * f.x - 1;
+            bound = A - 2LL * f.e1 - 1;
         }
         if (bound <= T) {
             const int i = atomicAdd(&nthreat, 1);
@@ -1389,15 +1316,23 @@ __global__ __launch_bounds__(256) void l2fr_final_kernel(
     if (tid == 0) out_count[p] = base;
 }
 
-// Debug dump of an intermediate record table into the match outputs (SFM_L2FR_DEBUG=1/2/3).
+// Debug dump of an intermediate record table into the match outputs (SFM_L2FR_DEBUG=1/2/3):
+// rec, or the packed forward records fwd8 decoded to (e1, e2, tile) when rec is null.
 __global__ void l2fr_dump_kernel(const int32_t* __restrict__ n_kp, const int32_t* __restrict__ pairs,
                                  int k_max, int k_pad, const int4* __restrict__ rec,
+                                 const rec8* __restrict__ fwd8,
                                  const int32_t* __restrict__ cnt, int32_t* __restrict__ out_count,
                                  int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
     const int p = blockIdx.x;
     const int n = cnt ? cnt[p] : n_kp[pairs[2 * p]];
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int4 r = rec[(size_t)p * k_pad + i];
+        int4 r;
+        if (rec) {
+            r = rec[(size_t)p * k_pad + i];
+        } else {
+            const l2fr::Fwd f = l2fr::unpack_fwd(fwd8[(size_t)p * k_pad + i]);
+            r = make_int4(f.e1, f.e2, f.tile, 0);
+        }
         out_match[((size_t)p * k_max + i) * 2] = r.x;
         out_match[((size_t)p * k_max + i) * 2 + 1] = r.y;
         out_dist[(size_t)p * k_max + i] = r.z;
@@ -1431,20 +1366,25 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     const size_t rinfob = sizeof(int4) * (size_t)n_rng_max * REC_R;
     const size_t sinfob = sfm::align_up(sizeof(int4) * (size_t)n_pairs, 256);
     const size_t uinfob = sfm::align_up(UNIT * sizeof(int4) * (size_t)n_pairs, 256);
-    const size_t flagb = sfm::align_up((size_t)n_pairs, 256);
-    // cfg4 in one launch (124 750 pairs x 4096): the three record tables 24.5 GB, cls 0.5 GB, the
-    // certificate's counts and flags 0.6 MB, everything else under 0.3 GB
-    char* ws = (char*)sfm::workspace(ctx, 256 + 2 * tab + 3 * recb + cntb + descb + 2 * ordb + clsb +
+    const size_t flagb = sfm::align_up((size_t)n_pairs, 256);  // the flags, then the pairs' smax
+    // cfg4 in one launch (124 750 pairs x 4096): the two 16-byte record tables 16.4 GB (the
+    // packed 8-byte forward and result records share the reverse scan's table, see below), cls
+    // 0.5 GB, the certificate's counts and flags 0.6 MB, everything else under 0.3 GB
+    char* ws = (char*)sfm::workspace(ctx, 256 + 2 * tab + 2 * recb + cntb + descb + 2 * ordb + clsb +
                                               256 + rngb + rinfob + 256 + sinfob + uinfob + 256 +
-                                              cntb + flagb);
+                                              cntb + flagb + cntb);
     if (!ws) return SFM_ERR_NOMEM;
     char* w = ws;
     uint8_t* zero_row = (uint8_t*)w; w += 256;
     int32_t* norm = (int32_t*)w; w += tab;
     int32_t* cinit = (int32_t*)w; w += tab;
-    int4* fwd = (int4*)w; w += recb;
     int4* surv = (int4*)w; w += recb;
     int4* rev = (int4*)w; w += recb;
+    // The packed forward records and the recovery's result records (8 bytes per query each) live
+    // in the two halves of the reverse scan's output table: their last reader (the certificate,
+    // or the compaction without it) is done before the reverse scan writes there.
+    rec8* fwd = (rec8*)rev;
+    rec8* qst = fwd + (size_t)n_pairs * k_pad;
     int32_t* scount = (int32_t*)w; w += cntb;
     uint8_t* desc_i8 = (uint8_t*)w; w += descb;
     int32_t* ord_f = (int32_t*)w; w += ordb;
@@ -1458,6 +1398,7 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     int32_t* n_units = (int32_t*)((char*)uinfo + uinfob);
     int32_t* rcount = (int32_t*)((char*)n_units + 256);  // reverse-scan survivor counts (certificate)
     uint8_t* flag = (uint8_t*)rcount + cntb;              // pairs the certificate left to the fallback
+    int32_t* smax = (int32_t*)(flag + flagb);             // largest survivor d1 of each pair
     // the forward scan by units of two pairs sharing their query image (build_units;
     // SFM_L2FR_UNITS=0: one pair per block, XCD-contiguous runs by train image)
     static const bool units_env = [] {
@@ -1482,50 +1423,43 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
                        n_pairs, n_img, ord_f, ord_r, rng, n_rng, rinfo, sinfo_f, unit_blk, uinfo,
                        n_units);
     SFM_HIP_CHECK(hipGetLastError());
-    // qst (per-query status of the recovery) shares the reverse scan's output buffer: it is
-    // consumed by the compaction before the reverse scan writes there.
-    int4* qst = rev;
-    const FwdCls fc{norm, prm->ratio_num, prm->ratio_den, (long long)prm->max_dist, qst, cls};
+    const FwdCls fc{norm, prm->ratio_num, prm->ratio_den, (long long)prm->max_dist, fwd, cls};
     hipLaunchKernelGGL(l2fr_scan_kernel<false>, dim3(grid), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp, k_max,
                        k_pad, cinit, zero_row, pairs, n_qblk, sord_f,
                        (const int4*)(units ? uinfo : sinfo_f), n_blk, (const int4*)nullptr,
-                       (const int32_t*)nullptr, fwd, fc, (const int32_t*)(units ? n_units : nullptr));
+                       (const int32_t*)nullptr, (int4*)nullptr, fc,
+                       (const int32_t*)(units ? n_units : nullptr));
     SFM_HIP_CHECK(hipGetLastError());
     const char* dbg = getenv("SFM_L2FR_DEBUG");
     const int dmode = dbg ? atoi(dbg) : 0;
     if (dmode == 1) {
         hipLaunchKernelGGL(l2fr_dump_kernel, dim3(n_pairs), dim3(256), 0, st, n_kp, pairs, k_max,
-                           k_pad, (const int4*)fwd, (const int32_t*)nullptr, out_count, out_match,
-                           out_dist);
+                           k_pad, (const int4*)nullptr, (const rec8*)fwd, (const int32_t*)nullptr,
+                           out_count, out_match, out_dist);
         return SFM_OK;
     }
-#ifdef L2FR_RECOVER_VALU
-    hipLaunchKernelGGL(l2fr_recover_kernel, dim3(n_pairs, k_pad / GROUP), dim3(256), 0, st, desc_i8,
-                       n_kp, k_max, k_pad, norm, cinit, pairs, fwd, (const uint8_t*)cls,
-                       prm->ratio_num, prm->ratio_den, (long long)prm->max_dist, qst);
-#else
-    hipLaunchKernelGGL(l2fr_recover_mfma_kernel, dim3(n_rng_max, k_pad / GROUP), dim3(256), 0, st,
+    hipLaunchKernelGGL(l2fr_recover_mfma_kernel, dim3(n_rng_max * (k_pad / GROUP)), dim3(256), 0, st,
                        desc_i8, k_max, k_pad, norm, cinit, (const int4*)rinfo, (const int32_t*)n_rng,
-                       (const int4*)fwd, (const uint8_t*)cls, prm->ratio_num, prm->ratio_den,
+                       (const rec8*)fwd, (const uint8_t*)cls, prm->ratio_num, prm->ratio_den,
                        (long long)prm->max_dist, qst);
-#endif
     SFM_HIP_CHECK(hipGetLastError());
     // the ratio rule alone: the compaction writes the output itself (no final kernel)
     const bool direct = !mutual && dmode == 0;
     hipLaunchKernelGGL(l2fr_compact_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, norm, pairs, qst, prm->ratio_num, prm->ratio_den,
-                       (long long)prm->max_dist, surv, scount, direct ? out_count : nullptr,
+                       k_pad, norm, pairs, (const uint8_t*)cls, qst, prm->ratio_num, prm->ratio_den,
+                       (long long)prm->max_dist, surv, scount, smax,
+                       direct ? out_count : nullptr,
                        out_match, out_dist);
     SFM_HIP_CHECK(hipGetLastError());
     if (direct) return SFM_OK;
     if (dmode == 2) {
         hipLaunchKernelGGL(l2fr_dump_kernel, dim3(n_pairs), dim3(256), 0, st, n_kp, pairs, k_max,
-                           k_pad, (const int4*)surv, (const int32_t*)scount, out_count, out_match,
-                           out_dist);
+                           k_pad, (const int4*)surv, (const rec8*)nullptr, (const int32_t*)scount,
+                           out_count, out_match, out_dist);
         return SFM_OK;
     }
     // mutual rule: the certificate decides every pair it can from the forward records (it reads
-    // qst before the reverse scan overwrites the aliased rev); the reverse scan and the final
+    // fwd and qst before the reverse scan overwrites the aliased rev); the reverse scan and the final
     // kernel then see only the flagged pairs (rcount = 0 / flag = 0 elsewhere: their blocks exit
     // at once).  SFM_L2FR_CERT=0: no certificate, every pair through the reverse scan.
     const char* ce = getenv("SFM_L2FR_CERT");
@@ -1537,8 +1471,9 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
         if (stats)  // the counters are the last call's
             SFM_HIP_CHECK(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), st));
         hipLaunchKernelGGL(l2fr_mutual_cert_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp,
-                           k_max, k_pad, norm, pairs, (const int4*)fwd, (const int4*)qst,
-                           (const int4*)surv, (const int32_t*)scount, cap, rcount, flag, stats,
+                           k_max, k_pad, norm, pairs, (const rec8*)fwd, (const uint8_t*)cls,
+                           (const rec8*)qst, (const int4*)surv, (const int32_t*)scount,
+                           (const int32_t*)smax, cap, rcount, flag, stats,
                            out_count, out_match, out_dist);
         SFM_HIP_CHECK(hipGetLastError());
     }
@@ -1552,8 +1487,8 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     }
     if (dmode == 3) {
         hipLaunchKernelGGL(l2fr_dump_kernel, dim3(n_pairs), dim3(256), 0, st, n_kp, pairs, k_max,
-                           k_pad, (const int4*)rev, (const int32_t*)scount, out_count, out_match,
-                           out_dist);
+                           k_pad, (const int4*)rev, (const rec8*)nullptr, (const int32_t*)scount,
+                           out_count, out_match, out_dist);
         return SFM_OK;
     }
     hipLaunchKernelGGL(l2fr_final_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
