@@ -510,6 +510,11 @@ int sfm_calib_mfma_i8(sfm_ctx* ctx, float target_ms, double* out);
  * exact dot products it took).  Off: the kernels take no counter pointer at all. */
 int sfm_match_cert_stats(sfm_ctx* ctx, int32_t enable, uint64_t* out);
 
+/* The grid bound of that path's fallback (reverse scan and final kernel): their blocks stride over
+ * the (query block, flagged pair) units, so a call that flags more units than this runs the stride
+ * loop more than once. */
+int32_t sfm_l2fr_rev_grid(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@
 //     exactly; if e1 > e2 the unique train with e == e1 is the nearest neighbour j1 and d1 is
 //     exact; the ratio test is decided exactly unless d2's unit ambiguity straddles it; ties
 //     (e1 == e2) and straddles take an exact full-row scan (rare);
-//   * certificate (mutual only, l2fr_mutual_cert_kernel): the cross check of a pair's survivors
+//   * certificate (mutual only, inside l2fr_tail_kernel): the cross check of a pair's survivors
 //     decided from the forward records' bounds, an owner table over the trains and exact dot
 //     products for the few (threat, survivor) pairs the bounds leave open; a pair with too many
 //     of those is flagged for the reverse scan (on descriptor data: none);
@@ -142,10 +142,11 @@ __device__ __forceinline__ void prep_one(int img, int j, const uint8_t* __restri
     cinit[o] = (j < n_kp[img]) ? -((nv + 1) >> 1) : PAD_INIT;
 }
 
-// Pair orders by streamed image, counting sort in LDS: block 0 orders by pairs[p][1] (forward
-// scan) into order_f, block 1 by pairs[p][0] (reverse scan) into order_r.
-// Block 0 also cuts order_f into recovery ranges: runs of at most REC_R consecutive entries with
-// the same train image, rng[r] = (first entry, length), *n_rng of them, and their pairs (rinfo).
+// Pair order by streamed image, counting sort in LDS: order block 0 orders by pairs[p][1] (forward
+// scan) into order_f, zeroes the flagged-pair count n_rng[1] of this call (the tail kernel appends,
+// the reverse scan and the final kernel read it) and cuts order_f into recovery ranges: runs of at
+// most REC_R consecutive entries with the same train image, rng[r] = (first entry, length), *n_rng
+// of them, and their pairs (rinfo).
 constexpr int REC_R = 4;  // pairs (sharing their train image) per recovery block
 
 // The forward scan's UNITS (order block unit_blk of l2fr_setup_kernel): the pairs grouped by query image
@@ -208,7 +209,7 @@ __device__ void build_units(const int32_t* __restrict__ pairs, int n_pairs, int 
 }
 
 __device__ void order_block(int ob, const int32_t* __restrict__ pairs, int n_pairs, int n_img,
-                            int32_t* __restrict__ order_f, int32_t* __restrict__ order_r,
+                            int32_t* __restrict__ order,
                             int2* __restrict__ rng, int32_t* __restrict__ n_rng,
                             const int32_t* __restrict__ n_kp, int4* __restrict__ rinfo,
                             int4* __restrict__ sinfo_f, int unit_blk, int4* __restrict__ uinfo,
@@ -217,13 +218,12 @@ __device__ void order_block(int ob, const int32_t* __restrict__ pairs, int n_pai
         build_units(pairs, n_pairs, n_img, n_kp, uinfo, n_units, hist);
         return;
     }
-    const int tid = threadIdx.x, col = ob == 0 ? 1 : 0;
-    int32_t* order = ob == 0 ? order_f : order_r;
+    const int tid = threadIdx.x;
     for (int i = tid; i < n_img; i += 1024) hist[i] = 0;
     __syncthreads();
-    for (int p = tid; p < n_pairs; p += 1024) atomicAdd(&hist[pairs[2 * p + col]], 1);
+    for (int p = tid; p < n_pairs; p += 1024) atomicAdd(&hist[pairs[2 * p + 1]], 1);
     __syncthreads();
-    int* roff = hist + n_img;  // block 0: first recovery range of each train image
+    int* roff = hist + n_img;  // first recovery range of each train image
     if (tid == 0) {
         int off = 0, nr = 0;
         for (int i = 0; i < n_img; ++i) {
@@ -233,26 +233,24 @@ __device__ void order_block(int ob, const int32_t* __restrict__ pairs, int n_pai
             hist[i] = off;
             off += c;
         }
-        if (ob == 0) *n_rng = nr;
+        n_rng[0] = nr;
+        n_rng[1] = 0;
     }
     __syncthreads();
-    if (ob == 0)
-        for (int i = tid; i < n_img; i += 1024) {
-            const int c = (i + 1 < n_img ? hist[i + 1] : n_pairs) - hist[i];
-            for (int k = 0; k < c; k += REC_R)
-                rng[roff[i] + k / REC_R] = make_int2(hist[i] + k, min(REC_R, c - k));
-        }
-    __syncthreads();
+    for (int i = tid; i < n_img; i += 1024) {
+        const int c = (i + 1 < n_img ? hist[i + 1] : n_pairs) - hist[i];
+        for (int k = 0; k < c; k += REC_R)
+            rng[roff[i] + k / REC_R] = make_int2(hist[i] + k, min(REC_R, c - k));
+    }
     __syncthreads();
     for (int p = tid; p < n_pairs; p += 1024) {
         const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        const int slot = atomicAdd(&hist[col ? b : a], 1);
+        const int slot = atomicAdd(&hist[b], 1);
         order[slot] = p;
-        // block 0: the forward scan's per-slot pair record, so its blocks start after ONE
-        // dependent load instead of the pair_order -> pairs -> n_kp chain
-        if (ob == 0) sinfo_f[slot] = make_int4(p, a, b, n_kp[a] | (n_kp[b] << 16));
+        // the forward scan's per-slot pair record, so its blocks start after ONE dependent load
+        // instead of the pair_order -> pairs -> n_kp chain
+        sinfo_f[slot] = make_int4(p, a, b, n_kp[a] | (n_kp[b] << 16));
     }
-    if (ob != 0) return;
     // the recovery ranges' pairs: rinfo[r][e] = (p, a, b, n_kp[a] | n_kp[b] << 16), p = -1 past
     // the range's length (order_f and rng come from this block: visible after the barrier)
     __threadfence_block();
@@ -274,14 +272,14 @@ __device__ void order_block(int ob, const int32_t* __restrict__ pairs, int n_pai
 
 // The ratio path's set-up in ONE launch of 1024-thread blocks: blocks [0, n_prep) convert the
 // descriptors (prep_one: the i8 rows, |x'|^2, the scan's accumulator init; bpi blocks per image),
-// the n_order blocks after them sort the pairs (order_block), concurrently with the conversion —
+// the blocks after them sort the pairs (order_block, build_units), concurrently with the conversion —
 // the two are independent, and the order blocks' latency-bound serial prefix no longer waits its
 // own launch (round 6: prep 10.4 + order 9.0 us as two launches at cfg2).
 __global__ __launch_bounds__(1024) void l2fr_setup_kernel(
     int n_prep, int bpi, const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp,
     int k_max, int k_pad, int32_t* __restrict__ norm, int32_t* __restrict__ cinit,
     uint8_t* __restrict__ zero_row, uint4* __restrict__ desc_i8, const int32_t* __restrict__ pairs,
-    int n_pairs, int n_img, int32_t* __restrict__ order_f, int32_t* __restrict__ order_r,
+    int n_pairs, int n_img, int32_t* __restrict__ order_f,
     int2* __restrict__ rng, int32_t* __restrict__ n_rng, int4* __restrict__ rinfo,
     int4* __restrict__ sinfo_f, int unit_blk, int4* __restrict__ uinfo,
     int32_t* __restrict__ n_units) {
@@ -293,7 +291,7 @@ __global__ __launch_bounds__(1024) void l2fr_setup_kernel(
                  cinit, zero_row, desc_i8);
         return;
     }
-    order_block(b - n_prep, pairs, n_pairs, n_img, order_f, order_r, rng, n_rng, n_kp, rinfo,
+    order_block(b - n_prep, pairs, n_pairs, n_img, order_f, rng, n_rng, n_kp, rinfo,
                 sinfo_f, unit_blk, uinfo, n_units, hist);
 }
 
@@ -325,7 +323,7 @@ constexpr int L2FR_CLOCK_SLOTS = 1 << 16;
 constexpr int L2FR_CLOCK_W = 24;
 __device__ unsigned long long g_l2fr_clock[L2FR_CLOCK_W * L2FR_CLOCK_SLOTS];
 #define L2FR_STAMP(i, v) \
-    if (!REV && tid == 0 && blockIdx.x < L2FR_CLOCK_SLOTS) g_l2fr_clock[L2FR_CLOCK_W * (size_t)blockIdx.x + (i)] = (v)
+    if (!REV && tid == 0 && bid < L2FR_CLOCK_SLOTS) g_l2fr_clock[L2FR_CLOCK_W * (size_t)bid + (i)] = (v)
 #else
 #define L2FR_STAMP(i, v)
 #endif
@@ -341,8 +339,13 @@ __device__ unsigned long long g_l2fr_clock[L2FR_CLOCK_W * L2FR_CLOCK_SLOTS];
 // tile and query tile: 4 MFMAs whose accumulator starts at the trains' -ceil(|y'|^2/2), then the
 // top-2 network ts = max(ts, med3(tb, x, y)), tb = max3(tb, x, y) — 1.5 VALU per element, no key
 // build, no column side.
+//
+// scan_body is one workgroup's work: the forward kernel runs it once for its block bid of n_bid;
+// the reverse kernel runs it for unit bid = query block * n_list + entry of the flagged-pair list
+// (pair_order = the list, n_list its length).
 template <bool REV>
-__global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_kernel(
+__device__ __forceinline__ void scan_body(
+    const unsigned bid, const unsigned n_bid, const int n_list,
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ cinit, const uint8_t* __restrict__ zero_row,
     const int32_t* __restrict__ pairs, int n_qblk, const int32_t* __restrict__ pair_order,
@@ -362,9 +365,9 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_kernel
         // the blocks past the units exit at once.
         const int nu = *n_units;
         const int u8 = (nu + 7) >> 3;
-        const int l = (int)(blockIdx.x >> 3);
+        const int l = (int)(bid >> 3);
         qb = u8 > 0 ? l / u8 : n_qblk;
-        pos = (l - qb * u8) * 8 + (int)(blockIdx.x & 7);
+        pos = (l - qb * u8) * 8 + (int)(bid & 7);
         if (qb >= n_qblk || pos >= nu) return;  // block-uniform, before any barrier
         const int4 u = sinfo[(size_t)UNIT * pos];
         asm volatile("" : : "s"(u.x), "s"(u.y), "s"(u.z), "s"(u.w));
@@ -373,32 +376,33 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_kernel
         ti = u.z;
         nq = u.w & 0xFFFF;
         nb = u.w >> 16;   // > 0: build_units places only pairs with rows on both sides
+    } else if (REV) {
+        // all the listed pairs' query block 0s first, then block 1s (mostly empty)
+        qb = (int)bid / n_list;
+        p = pair_order[(int)bid - qb * n_list];
+        qi = pairs[2 * p + 1];
+        ti = pairs[2 * p];
+        nq = qcount[p];
+        nb = n_kp[ti];
     } else {
         // XCD-aware block order: workgroups go round-robin over the 8 XCDs (blockIdx % 8); XCD x
         // owns the x-th contiguous run of ppx pairs of pair_order (pairs sharing the streamed image
         // are adjacent, so its L2 serves them) and runs all their query block 0s first, then block
-        // 1s (in the reverse scan most block 1s are empty and exit at once, after the real work).
-        const int ppx = (int)(gridDim.x >> 3) / n_qblk;
-        const int l = (int)(blockIdx.x >> 3);
-        const int pos = (int)(blockIdx.x & 7) * ppx + l % ppx;
+        // 1s.
+        const int ppx = (int)(n_bid >> 3) / n_qblk;
+        const int l = (int)(bid >> 3);
+        const int pos = (int)(bid & 7) * ppx + l % ppx;
         qb = l / ppx;
         if (pos >= n_blk) return;  // block-uniform, before any barrier
-        if (REV) {
-            p = pair_order[pos];
-            qi = pairs[2 * p + 1];
-            ti = pairs[2 * p];
-            nq = qcount[p];
-            nb = n_kp[ti];
-        } else {  // one record (order kernel): pair, query image, train image, both counts
-            const int4 u = sinfo[pos];
-            // all four fields before the early exit: one s_load_dwordx4, not two dependent loads
-            asm volatile("" : : "s"(u.x), "s"(u.y), "s"(u.z), "s"(u.w));
-            p = u.x;
-            qi = u.y;
-            ti = u.z;
-            nq = u.w & 0xFFFF;
-            nb = u.w >> 16;
-        }
+        // one record (order kernel): pair, query image, train image, both counts
+        const int4 u = sinfo[pos];
+        // all four fields before the early exit: one s_load_dwordx4, not two dependent loads
+        asm volatile("" : : "s"(u.x), "s"(u.y), "s"(u.z), "s"(u.w));
+        p = u.x;
+        qi = u.y;
+        ti = u.z;
+        nq = u.w & 0xFFFF;
+        nb = u.w >> 16;
     }
     if (qb * QB >= nq || nb <= 0) return;  // block-uniform
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
@@ -705,6 +709,34 @@ __global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_kernel
 #endif
 }
 
+__global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_fwd_kernel(
+    const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
+    const int32_t* __restrict__ cinit, const uint8_t* __restrict__ zero_row,
+    const int32_t* __restrict__ pairs, int n_qblk, const int4* __restrict__ sinfo, int n_blk,
+    FwdCls fc, const int32_t* __restrict__ n_units) {
+    scan_body<false>(blockIdx.x, gridDim.x, 0, desc, n_kp, k_max, k_pad, cinit, zero_row, pairs, n_qblk,
+                     nullptr, sinfo, n_blk, nullptr, nullptr, nullptr, fc, n_units);
+}
+
+// The reverse scan of the flagged pairs (flist[0 .. *n_flag - 1], written by the tail kernel) on a
+// bounded grid: the blocks stride over the (query block, listed pair) units, so a call with nothing
+// flagged costs one launch of blocks that read the count and exit.  Which block serves which pair
+// reaches no result.
+constexpr int REV_GRID = 1024;
+__global__ __launch_bounds__(SCAN_THREADS, SCAN_MIN_WAVES) void l2fr_scan_rev_kernel(
+    const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
+    const int32_t* __restrict__ cinit, const uint8_t* __restrict__ zero_row,
+    const int32_t* __restrict__ pairs, int n_qblk, const int32_t* __restrict__ flist,
+    const int32_t* __restrict__ n_flag, const int4* __restrict__ qlist,
+    const int32_t* __restrict__ qcount, int4* __restrict__ out) {
+    const int nl = *n_flag;
+    for (unsigned u = blockIdx.x; u < (unsigned)(nl * n_qblk); u += gridDim.x) {
+        scan_body<true>(u, 0, nl, desc, n_kp, k_max, k_pad, cinit, zero_row, pairs, n_qblk, flist,
+                        nullptr, 0, qlist, qcount, out, FwdCls{}, nullptr);
+        __syncthreads();   // the next unit restages the LDS this one's last tiles were read from
+    }
+}
+
 // Exact (d1, j1, d2) of one query over all trains (multiset second, lowest-index j1), block-wide.
 // Returns through LDS slot `res` (valid for every thread after the call).
 struct Top2 { long long b1; int j1; long long b2; };
@@ -983,106 +1015,29 @@ __global__ __launch_bounds__(256, REC_SB > 2 ? 2 : 3) void l2fr_recover_mfma_ker
     }
 }
 
-// Exact full-row scans for the SLOW queries (ties in e, straddled ratio decisions: rare), then the
-// ordered compaction of the survivors (q, j1, d1, 0) into surv[p][0..scount[p]-1] (block of 256
-// per pair).  The class byte says what a query has: a candidate (tile) its result record from the
-// recovery, a slow one (CLS_SLOW) nothing yet, a dropped one (CLS_DROP) nothing at all.  A query
-// resolved by a row scan gets its exact record into qst as (status, j1, d1, exact = 1), whatever
-// its ratio verdict: after this kernel every query with cls != CLS_DROP has a record, and its exact
-// flag marks the queries whose (j1, d1) is exact (the mutual certificate's "known" queries).
-__global__ __launch_bounds__(256) void l2fr_compact_kernel(
-    const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
-    const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
-    const uint8_t* __restrict__ cls, rec8* __restrict__ qst, int rnum, int rden, long long max_dist,
-    int4* __restrict__ surv, int32_t* __restrict__ scount, int32_t* __restrict__ smax,
-    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
-    int32_t* __restrict__ out_dist) {
-    __shared__ Top2 red[256];
-    __shared__ int slow[256];
-    __shared__ int nslow, wsum[8], wmax[4];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int a = pairs[2 * p], b = pairs[2 * p + 1];
-    const int na = n_kp[a], nb = n_kp[b];
-    // out_count != nullptr (the ratio rule without cross check): the survivors ARE the output —
-    // the final kernel's copy of them in the same order, written here instead of surv
-    const bool direct = out_count != nullptr;
-    int32_t* om = direct ? out_match + (size_t)p * k_max * 2 : nullptr;
-    int32_t* od = direct ? out_dist + (size_t)p * k_max : nullptr;
-    if (na <= 0 || nb <= 0) {
-        if (tid == 0) {
-            if (direct) out_count[p] = 0;
-            else scount[p] = 0;
-        }
-        return;
-    }
-    rec8* qs = qst + (size_t)p * k_pad;
-    const uint8_t* cl = cls + (size_t)p * k_pad;
-    const int32_t* na_norm = norm + (size_t)a * k_pad;
-    const int32_t* nb_norm = norm + (size_t)b * k_pad;
-    const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
-    const uint8_t* db = desc + (size_t)b * k_max * D;
-    int4* sv = surv + (size_t)p * k_pad;
-    int base = 0, dmax = 0;   // dmax: this thread's largest survivor d1
-    for (int q0 = 0; q0 < na; q0 += 256) {
-        const int q = q0 + tid;
-        int4 r = make_int4(ST_DROP, 0, 0, 0);   // (status, j1, d1, exact)
-        if (q < na) {
-            // both loads at once (no round trip for the class byte first): the result slot of a
-            // query that is no candidate holds stale bytes, read and ignored
-            const unsigned char c = cl[q];
-            const rec8 raw = qs[q];
-            if (c == l2fr::CLS_SLOW) {
-                r.x = ST_SLOW;
-            } else if (c != l2fr::CLS_DROP) {
-                const l2fr::Res u = l2fr::unpack_res(raw);
-                r = make_int4(u.st, u.j1, u.d1, u.exact);
-            }
-        }
-        if (tid == 0) nslow = 0;
-        __syncthreads();
-        if (r.x == ST_SLOW) slow[atomicAdd(&nslow, 1)] = tid;
-        __syncthreads();
-        const int ns = nslow;
-        for (int i = 0; i < ns; ++i) {
-            const int who = slow[i], qq = q0 + who;
-            const Top2 e = exact_row_scan(qa + (size_t)qq * SLOTS, db, nb_norm, nb, na_norm[qq], red);
-            if (tid == who) {
-                bool keep = sfm::ratio_ok(e.b1, e.b2, rnum, rden, true);
-                keep = keep && (max_dist < 0 || e.b1 < max_dist);
-                r = make_int4(keep ? ST_PASS : ST_DROP, e.j1, (int)e.b1, 1);
-                if (!direct) qs[qq] = l2fr::pack_res(r.x, r.y, r.z, 1);
-            }
-        }
-        const bool keep = r.x == ST_PASS;
-        dmax = keep ? max(dmax, r.z) : dmax;
-        if (direct)
-            base = sfm::compact256(keep, q, r.y, r.z, base, wsum, om, od);
-        else
-            base = compact_rec(keep, make_int4(q, r.y, r.z, 0), base, wsum, sv);
-    }
-    if (tid == 0) {
-        if (direct) out_count[p] = base;
-        else scount[p] = base;
-    }
-    if (direct) return;
-    // the largest survivor d1 (the certificate's T), so that it need not walk surv for it
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) dmax = max(dmax, __shfl_xor(dmax, m));
-    if ((tid & 63) == 0) wmax[tid >> 6] = dmax;
-    __syncthreads();
-    if (tid == 0) smax[p] = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
-}
-
-// Mutual certificate (block of 256 per pair, after the compaction): decides the cross check of the
-// pair's survivors from what the forward scan already holds, in place of the reverse scan + final
-// kernel (DESIGN.md §4.1 "certificate").
+// The tail of a pair after the recovery, one block of 256 per pair: exact row scans for the SLOW
+// queries, the ordered list of the ratio survivors and, for the mutual rule, the certificate of
+// their cross check (DESIGN.md §4.1 "certificate").
+//
+// Every thread loads the class byte, result record, forward record and |x'|^2 of its TAIL_NQ
+// queries (q = 256 i + tid) up front, as independent loads; the survivors' count, their ordered
+// slots and T = max d1 come from ballots and one block prefix over registers.  The class byte says
+// what a query has: a candidate (tile) its result record from the recovery, a slow one (CLS_SLOW)
+// nothing yet, a dropped one (CLS_DROP) nothing at all.  SLOW queries (ties in e, straddled ratio
+// decisions: rare) take an exact full-row scan; its record (status, j1, d1, exact = 1) goes
+// through qst back to the thread that owns the query.
+//
+// TAIL_DIRECT (the ratio rule alone): the survivors ARE the output, written in query order.
+// TAIL_SPILL (SFM_L2FR_CERT=0 and the debug dumps): the survivors (q, j1, d1, 0) go to
+// surv[p][0..scount[p]-1] and the pair joins the flagged list: the reverse scan decides it.
+// TAIL_CERT (mutual rule): the certificate.
 //
 // Survivor (q, j, d1) — j its lowest-index nearest train, d1 exact — is a mutual match iff no
 // query q' != q has (d(q', j), q') < (d1, q) lexicographically.  Per query q' (A' = |x'_q'|^2,
 // forward record (e1', e2'), d = A' - 2e - (|y'|^2 mod 2)):
-//   * known q' (qst.w == 1: exact (j1', d1') from the recovery or a row scan): d(q', j1') = d1',
-//     and every other train has e <= e2' (e2' the multiset second), so d(q', j) >= L2' =
-//     A' - 2 e2' - 1 (+inf when e2' is no real element);
+//   * known q' (exact (j1', d1') from the recovery or a row scan): d(q', j1') = d1', and every
+//     other train has e <= e2' (e2' the multiset second), so d(q', j) >= L2' = A' - 2 e2' - 1
+//     (+inf when e2' is no real element);
 //   * unknown q' (dropped by the scan's interval test): every train has d(q', j) >= L1' =
 //     A' - 2 e1' - 1.
 // So (1) an owner table over the trains takes min (d1' << 32 | q') over the known queries at
@@ -1090,11 +1045,12 @@ __global__ __launch_bounds__(256) void l2fr_compact_kernel(
 // query whose bound (L2' resp. L1') is <= T — can beat a survivor at a train that is not its own
 // j1', and only a survivor with d1 >= that bound: those (threat, survivor) pairs get one exact
 // dot product each.  On ratio-test survivors of descriptor data there are none (survivor d1 is far
-// below everybody's second distance: that is what passing the test means).
-// A pair whose threats x survivors exceed `cap` (or whose threats do not fit the list) is flagged
-// instead: flag[p] = 1, rcount[p] = scount[p], and the reverse scan + final kernel decide it.
-// Every other pair gets rcount[p] = 0 (its reverse-scan blocks exit at once) and its output here,
-// in the final kernel's order.  stats (nullptr: off): pairs certified, pairs flagged, exact dots.
+// below everybody's second distance: that is what passing the test means), and then the survivors
+// never leave the registers: the output is written from them in the final kernel's order.
+// A pair with threats spills its survivors to surv for the walk.  A pair whose threats x
+// survivors exceed `cap` (or whose threats do not fit the list) is flagged instead: its survivors
+// and scount[p] go to memory, the pair to flist[atomicAdd(n_flag)], and the reverse scan + final
+// kernel decide it.  stats (nullptr: off): pairs certified, pairs flagged, exact dots.
 constexpr int CERT_TMAX = 2048;  // threat list entries (LDS)
 // Default cap on threats x survivors of one pair.  One unit is a list walk step (an LDS read, a
 // 16-byte survivor read, a compare) and at most one exact 128-byte dot product with two dependent
@@ -1107,151 +1063,316 @@ constexpr int CERT_TMAX = 2048;  // threat list entries (LDS)
 // five times that at the measured mix.  16384 sits at the low end of that band.
 // Override: SFM_L2FR_CERT_CAP (0: every pair takes the fallback).
 constexpr long long CERT_CAP_DEFAULT = 16384;
+constexpr int TAIL_NQ = KMAX / 256;  // queries per thread
+enum : int { TAIL_DIRECT = 0, TAIL_CERT = 1, TAIL_SPILL = 2 };
 
-__global__ __launch_bounds__(256) void l2fr_mutual_cert_kernel(
+template <int MODE>
+__global__ __launch_bounds__(256, 3) void l2fr_tail_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ pairs,
-    const rec8* __restrict__ fwd, const uint8_t* __restrict__ cls, const rec8* __restrict__ qst,
-    const int4* __restrict__ surv, const int32_t* __restrict__ scount,
-    const int32_t* __restrict__ smax, long long cap, int32_t* __restrict__ rcount,
-    uint8_t* __restrict__ flag, unsigned long long* __restrict__ stats,
-    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
-    int32_t* __restrict__ out_dist) {
+    const rec8* __restrict__ fwd, const uint8_t* __restrict__ cls, rec8* qst, int rnum, int rden,
+    long long max_dist, long long cap, int4* surv, int32_t* __restrict__ scount,
+    int32_t* __restrict__ flist, int32_t* __restrict__ n_flag,
+    unsigned long long* __restrict__ stats, int32_t* __restrict__ out_count,
+    int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
+    // The owner table's 32 KB also serve the row scans, which are done before the table is built:
+    // their reduction slots in its first 8 KB, the list of slow queries in its second.
     __shared__ unsigned long long owner[KMAX];
     __shared__ int tbound[CERT_TMAX];
     __shared__ unsigned short tq[CERT_TMAX];
     __shared__ unsigned char killed[KMAX];
-    __shared__ int wsum[8];
-    __shared__ int nthreat;
-    const int p = blockIdx.x, tid = threadIdx.x;
+    __shared__ __attribute__((aligned(16))) int wcnt[TAIL_NQ][4];
+    __shared__ int wmax[4];
+    __shared__ int nthreat, nslow;
+    Top2* red = (Top2*)owner;
+    unsigned short* slowq = (unsigned short*)(owner + 1024);
+    static_assert(sizeof(Top2) * 256 <= 8192, "the row scan's slots overlap the slow list");
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
     const int na = n_kp[a], nb = n_kp[b];
-    const int S = (na > 0 && nb > 0) ? scount[p] : 0;
-    if (cap <= 0) {  // every pair through the reverse scan
+    if (na <= 0 || nb <= 0) {   // block-uniform: no records at all, no survivors
         if (tid == 0) {
-            rcount[p] = S;
-            flag[p] = 1;
-            if (stats) atomicAdd(&stats[1], 1ull);
+            if (MODE == TAIL_SPILL || (MODE == TAIL_CERT && cap <= 0)) {
+                scount[p] = 0;
+                flist[atomicAdd(n_flag, 1)] = p;
+                if (MODE == TAIL_CERT && stats) atomicAdd(&stats[1], 1ull);
+            } else {
+                out_count[p] = 0;
+                if (MODE == TAIL_CERT && stats) atomicAdd(&stats[0], 1ull);
+            }
         }
         return;
     }
-    if (S == 0) {  // nothing to decide
+    const int nq = na;
+    rec8* qs = qst + (size_t)p * k_pad;
+    const rec8* fw = fwd + (size_t)p * k_pad;
+    const uint8_t* cl = cls + (size_t)p * k_pad;
+    const int32_t* na_norm = norm + (size_t)a * k_pad;
+    const int32_t* nb_norm = norm + (size_t)b * k_pad;
+    const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
+    const uint4* dbv = (const uint4*)(desc + (size_t)b * k_max * D);
+    int4* sv = surv + (size_t)p * k_pad;
+    int32_t* om = out_match + (size_t)p * k_max * 2;
+    int32_t* od = out_dist + (size_t)p * k_max;
+
+    // all loads at once; the result slot of a query that is no candidate holds stale bytes, read
+    // and ignored
+    // Per query: the result record; has = it has or will have one (class != CLS_DROP: after the
+    // row scans every such query's (j1, d1) is exact, the certificate's "known" queries); slow =
+    // SLOW by class, or left so by the recovery (a straddled ratio decision); bnd = the
+    // certificate's bound on its distance to any train that is not its j1 (INT_MAX: none).
+    // The loads in two rounds of TAIL_NQ / 2 queries, each round's unconditional and independent
+    // (a query past nq repeats query nq - 1 and is masked out).
+    rec8 raw[TAIL_NQ];
+    int bnd[TAIL_NQ];
+    unsigned hasm = 0, slowm = 0;
+#pragma unroll
+    for (int i0 = 0; i0 < TAIL_NQ; i0 += TAIL_NQ / 2) {
+        if (i0 * 256 >= nq) {   // block-uniform (k_max <= 2048): nothing in this round
+#pragma unroll
+            for (int i = i0; i < i0 + TAIL_NQ / 2; ++i) {
+                raw[i] = 0;
+                bnd[i] = INT_MAX;
+            }
+            continue;
+        }
+        unsigned char c[TAIL_NQ / 2];
+        rec8 fr[TAIL_NQ / 2];
+        int A[TAIL_NQ / 2];
+#pragma unroll
+        for (int k = 0; k < TAIL_NQ / 2; ++k) {
+            const int qc = min((i0 + k) * 256 + tid, nq - 1);
+            c[k] = cl[qc];
+            raw[i0 + k] = qs[qc];
+            if (MODE == TAIL_CERT) {
+                fr[k] = fw[qc];
+                A[k] = na_norm[qc];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < TAIL_NQ / 2; ++k) {
+            const int i = i0 + k;
+            const bool in = i * 256 + tid < nq;
+            const bool has = in && c[k] != l2fr::CLS_DROP;
+            const bool slow =
+                in && (c[k] == l2fr::CLS_SLOW || (has && l2fr::unpack_res(raw[i]).st == ST_SLOW));
+            hasm |= has ? 1u << i : 0u;
+            slowm |= slow ? 1u << i : 0u;
+            bnd[i] = INT_MAX;
+            if (MODE == TAIL_CERT) {
+                const l2fr::Fwd f = l2fr::unpack_fwd(fr[k]);
+                // known: every train but j1 has e <= e2 (the multiset second); unknown: e <= e1
+                const int known = f.e2 > E_VALID ? A[k] - 2 * f.e2 - 1 : INT_MAX;
+                bnd[i] = !in ? INT_MAX : (has ? known : A[k] - 2 * f.e1 - 1);
+            }
+        }
+    }
+    if (tid == 0) nslow = 0;
+    if (__syncthreads_or(slowm != 0)) {   // block-uniform; rare
+#pragma unroll
+        for (int i = 0; i < TAIL_NQ; ++i)
+            if ((slowm >> i) & 1u) slowq[atomicAdd(&nslow, 1)] = (unsigned short)(i * 256 + tid);
+        __syncthreads();
+        const int ns = nslow;
+        for (int k = 0; k < ns; ++k) {
+            const int qq = slowq[k];
+            const Top2 e = exact_row_scan(qa + (size_t)qq * SLOTS, (const uint8_t*)dbv, nb_norm, nb,
+                                          na_norm[qq], red);
+            if (tid == (qq & 255)) {   // the query's owner
+                bool keep = sfm::ratio_ok(e.b1, e.b2, rnum, rden, true);
+                keep = keep && (max_dist < 0 || e.b1 < max_dist);
+                qs[qq] = l2fr::pack_res(keep ? ST_PASS : ST_DROP, e.j1, (int)e.b1, 1);
+            }
+        }
+        __syncthreads();   // the row scans' LDS is the owner table's from here on
+#pragma unroll
+        for (int i = 0; i < TAIL_NQ; ++i)
+            if ((slowm >> i) & 1u) raw[i] = qs[i * 256 + tid];   // the owner's own store above
+    }
+    // the survivors: their number per (round, wave) and the largest d1
+    unsigned keepm = 0;
+    int dmax = 0;
+#pragma unroll
+    for (int i = 0; i < TAIL_NQ; ++i) {
+        const l2fr::Res r = l2fr::unpack_res(raw[i]);
+        const bool keep = ((hasm >> i) & 1u) && r.st == ST_PASS;
+        keepm |= keep ? 1u << i : 0u;
+        dmax = keep ? max(dmax, r.d1) : dmax;
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wcnt[i][wave] = __popcll(bal);
+    }
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) dmax = max(dmax, __shfl_xor(dmax, m));
+    if (lane == 0) wmax[wave] = dmax;
+    if (MODE == TAIL_CERT) {   // the tables start empty
+        for (int k = tid; k < nq; k += 256) killed[k] = 0;
+        for (int j = tid; j < nb; j += 256) owner[j] = ~0ull;
+        if (tid == 0) nthreat = 0;
+    }
+    __syncthreads();
+    // ordered slots: survivors of earlier rounds, of earlier waves of the round, of earlier lanes
+    unsigned slot2[TAIL_NQ / 2] = {};   // two 16-bit slots per register
+    auto slot = [&](int i) { return (int)((slot2[i >> 1] >> (16 * (i & 1))) & 0xFFFFu); };
+    int S = 0;
+#pragma unroll
+    for (int i = 0; i < TAIL_NQ; ++i) {
+        const int4 w4 = *(const int4*)wcnt[i];
+        const int ww[4] = {w4.x, w4.y, w4.z, w4.w};
+        int off = S;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            off += w < wave ? ww[w] : 0;
+            S += ww[w];
+        }
+        const unsigned long long bal = __ballot((keepm >> i) & 1u);
+        slot2[i >> 1] |= (unsigned)(off + __popcll(bal & ((1ull << lane) - 1ull))) << (16 * (i & 1));
+    }
+    const int T = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+
+    if (MODE == TAIL_DIRECT) {
+#pragma unroll
+        for (int i = 0; i < TAIL_NQ; ++i)
+            if ((keepm >> i) & 1u) {
+                const l2fr::Res r = l2fr::unpack_res(raw[i]);
+                om[2 * slot(i)] = i * 256 + tid;
+                om[2 * slot(i) + 1] = r.j1;
+                od[slot(i)] = r.d1;
+            }
+        if (tid == 0) out_count[p] = S;
+        return;
+    }
+    auto spill = [&]() {   // the survivors to memory, in order
+#pragma unroll
+        for (int i = 0; i < TAIL_NQ; ++i)
+            if ((keepm >> i) & 1u) {
+                const l2fr::Res r = l2fr::unpack_res(raw[i]);
+                sv[slot(i)] = make_int4(i * 256 + tid, r.j1, r.d1, 0);
+            }
+    };
+    auto flag_pair = [&]() {   // the reverse scan + final kernel decide this pair
+        spill();
         if (tid == 0) {
-            rcount[p] = 0;
-            flag[p] = 0;
+            scount[p] = S;
+            flist[atomicAdd(n_flag, 1)] = p;
+            if (MODE == TAIL_CERT && stats) atomicAdd(&stats[1], 1ull);
+        }
+    };
+    if (MODE == TAIL_SPILL || cap <= 0) {  // every pair through the reverse scan
+        flag_pair();
+        return;
+    }
+    if (S == 0) {  // nothing to decide (block-uniform)
+        if (tid == 0) {
             out_count[p] = 0;
             if (stats) atomicAdd(&stats[0], 1ull);
         }
         return;
     }
-    const rec8* fw = fwd + (size_t)p * k_pad;
-    const rec8* qs = qst + (size_t)p * k_pad;
-    const uint8_t* cl = cls + (size_t)p * k_pad;
-    const int4* sv = surv + (size_t)p * k_pad;
-    const int32_t* na_norm = norm + (size_t)a * k_pad;
-    const int32_t* nb_norm = norm + (size_t)b * k_pad;
-    const uint4* qa = (const uint4*)(desc + (size_t)a * k_max * D);
-    const uint4* dbv = (const uint4*)(desc + (size_t)b * k_max * D);
-
-    // T = max d1 over the survivors (the compaction's smax); the tables start empty
-    const long long T = smax[p];
-    for (int k = tid; k < S; k += 256) killed[k] = 0;
-    for (int j = tid; j < nb; j += 256) owner[j] = ~0ull;
-    if (tid == 0) nthreat = 0;
-    __syncthreads();
-
     // owner table and threat list over all queries of image a
-    for (int q = tid; q < na; q += 256) {
-        // a dropped query has no result record (cls == CLS_DROP); every other one has (compaction)
-        // (the slot is read with the class byte, not after it: stale bytes there are ignored)
-        const unsigned char c = cl[q];
-        const rec8 raw = qs[q];
-        l2fr::Res r{ST_DROP, 0, 0, 0};
-        if (c != l2fr::CLS_DROP) r = l2fr::unpack_res(raw);
-        const l2fr::Fwd f = l2fr::unpack_fwd(fw[q]);
-        const long long A = na_norm[q];
-        long long bound;
-        if (r.exact == 1) {
+#pragma unroll
+    for (int i = 0; i < TAIL_NQ; ++i) {
+        const int q = i * 256 + tid;
+        if ((hasm >> i) & 1u) {
+            const l2fr::Res r = l2fr::unpack_res(raw[i]);
             if ((unsigned)r.j1 < (unsigned)nb)
                 atomicMin(&owner[r.j1], ((unsigned long long)(unsigned)r.d1 << 32) | (unsigned)q);
-            bound = f.e2 > E_VALID ? A - 2LL * f.e2 - 1 : sfm::DIST_INF;
-        } else {
-            bound = A - 2LL * f.e1 - 1;
         }
-        if (bound <= T) {
-            const int i = atomicAdd(&nthreat, 1);
-            if (i < CERT_TMAX) {
-                tq[i] = (unsigned short)q;
-                tbound[i] = (int)bound;
+        if (bnd[i] <= T) {   // no query past nq: its bound is INT_MAX
+            const int k = atomicAdd(&nthreat, 1);
+            if (k < CERT_TMAX) {
+                tq[k] = (unsigned short)q;
+                tbound[k] = bnd[i];
             }
         }
     }
     __syncthreads();
     const int nT = nthreat;
     if (nT > CERT_TMAX || (long long)nT * S > cap) {  // block-uniform: the fallback decides
-        if (tid == 0) {
-            rcount[p] = S;
-            flag[p] = 1;
-            if (stats) atomicAdd(&stats[1], 1ull);
-        }
+        flag_pair();
         return;
     }
-    // threats against survivors: exact distances where the bound does not already decide
-    unsigned dots = 0;
-    for (int i = tid; i < nT * S; i += 256) {
-        const int t = i / S, k = i - t * S;
-        const int4 s = sv[k];
-        const int qp = tq[t];
-        if (qp == s.x || s.z < tbound[t]) continue;
-        const int dot = dot128(qa + (size_t)qp * SLOTS, dbv + (size_t)s.y * SLOTS);
-        const long long d = (long long)na_norm[qp] + nb_norm[s.y] - 2LL * dot;
-        if (d < s.z || (d == s.z && qp < s.x)) killed[k] = 1;
-        ++dots;
-    }
-    if (stats && dots) atomicAdd(&stats[2], (unsigned long long)dots);
-    __syncthreads();
-    int32_t* om = out_match + (size_t)p * k_max * 2;
-    int32_t* od = out_dist + (size_t)p * k_max;
-    int base = 0;
-    for (int k0 = 0; k0 < S; k0 += 256) {
-        const int k = k0 + tid;
-        int4 s = make_int4(0, 0, 0, 0);
-        bool keep = false;
-        if (k < S) {
-            s = sv[k];
-            keep = !killed[k] &&
-                   owner[s.y] == (((unsigned long long)(unsigned)s.z << 32) | (unsigned)s.x);
+    if (nT > 0) {  // block-uniform
+        // threats against survivors: exact distances where the bound does not already decide;
+        // the walk indexes the survivors by slot, so they go through memory
+        spill();
+        __syncthreads();
+        unsigned dots = 0;
+        for (int i = tid; i < nT * S; i += 256) {
+            const int t = i / S, k = i - t * S;
+            const int4 s = sv[k];
+            const int qp = tq[t];
+            if (qp == s.x || s.z < tbound[t]) continue;
+            const int dot = dot128(qa + (size_t)qp * SLOTS, dbv + (size_t)s.y * SLOTS);
+            const long long d = (long long)na_norm[qp] + nb_norm[s.y] - 2LL * dot;
+            if (d < s.z || (d == s.z && qp < s.x)) killed[k] = 1;
+            ++dots;
         }
-        base = sfm::compact256(keep, s.x, s.y, s.z, base, wsum, om, od);
+        if (stats && dots) atomicAdd(&stats[2], (unsigned long long)dots);
+        __syncthreads();
+    }
+    // the mutual matches in query order: a second prefix over the registers
+    unsigned outm = 0;
+#pragma unroll
+    for (int i = 0; i < TAIL_NQ; ++i) {
+        bool keep = false;
+        if ((keepm >> i) & 1u) {
+            const l2fr::Res r = l2fr::unpack_res(raw[i]);
+            keep = !killed[slot(i)] &&
+                   owner[r.j1] == (((unsigned long long)(unsigned)r.d1 << 32) | (unsigned)(i * 256 + tid));
+        }
+        outm |= keep ? 1u << i : 0u;
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wcnt[i][wave] = __popcll(bal);
+    }
+    __syncthreads();
+    int M = 0;
+#pragma unroll
+    for (int i = 0; i < TAIL_NQ; ++i) {
+        const int4 w4 = *(const int4*)wcnt[i];
+        const int ww[4] = {w4.x, w4.y, w4.z, w4.w};
+        int off = M;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            off += w < wave ? ww[w] : 0;
+            M += ww[w];
+        }
+        const unsigned long long bal = __ballot((outm >> i) & 1u);
+        if ((outm >> i) & 1u) {
+            const int o = off + __popcll(bal & ((1ull << lane) - 1ull));
+            const l2fr::Res r = l2fr::unpack_res(raw[i]);
+            om[2 * o] = i * 256 + tid;
+            om[2 * o + 1] = r.j1;
+            od[o] = r.d1;
+        }
     }
     if (tid == 0) {
-        out_count[p] = base;
-        rcount[p] = 0;
-        flag[p] = 0;
+        out_count[p] = M;
         if (stats) atomicAdd(&stats[0], 1ull);
     }
 }
 
-// Mutual decision from the reverse scan + ordered output (block of 256 per pair).  flag != nullptr
-// (the certificate ran): only the pairs it flagged; the others have their output already.
+// Mutual decision from the reverse scan + ordered output, for the pairs of the flagged list (the
+// others have their output already): blocks of 256 on a bounded grid stride over the list.
 __global__ __launch_bounds__(256) void l2fr_final_kernel(
     const uint8_t* __restrict__ desc, const int32_t* __restrict__ n_kp, int k_max, int k_pad,
     const int32_t* __restrict__ norm, const int32_t* __restrict__ cinit,
     const int32_t* __restrict__ pairs, const int4* __restrict__ surv,
-    const int32_t* __restrict__ scount, const int4* __restrict__ rev, int mutual,
-    const uint8_t* __restrict__ flag, int32_t* __restrict__ out_count,
-    int32_t* __restrict__ out_match, int32_t* __restrict__ out_dist) {
+    const int32_t* __restrict__ scount, const int4* __restrict__ rev,
+    const int32_t* __restrict__ flist, const int32_t* __restrict__ n_flag,
+    int32_t* __restrict__ out_count, int32_t* __restrict__ out_match,
+    int32_t* __restrict__ out_dist) {
     __shared__ int wsum[8];
     __shared__ int amb[256];
     __shared__ int namb;
     __shared__ unsigned char keepx[256];
     __shared__ long long redd[256];
     __shared__ int redq[256];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    if (flag && !flag[p]) return;  // block-uniform
+    const int tid = threadIdx.x, nl = *n_flag;
+    for (int li = blockIdx.x; li < nl; li += gridDim.x) {  // block-uniform
+    const int p = flist[li];
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
-    const int na = n_kp[a], nb = n_kp[b];
-    const int S = (na > 0 && nb > 0) ? scount[p] : 0;
+    const int na = n_kp[a];
+    const int S = scount[p];
     const int4* sv = surv + (size_t)p * k_pad;
     const int4* rv = rev + (size_t)p * k_pad;
     const int32_t* na_norm = norm + (size_t)a * k_pad;
@@ -1270,14 +1391,11 @@ __global__ __launch_bounds__(256) void l2fr_final_kernel(
         __syncthreads();
         if (k < S) {
             s = sv[k];
-            keep = true;
-            if (mutual) {
-                const int4 r = rv[k];
-                const int dot = (int)(((long long)na_norm[s.x] + nb_norm[s.y] - s.z) >> 1);
-                const int ep = dot + ca[s.x];
-                keep = (ep == r.x) && (r.y < r.x);
-                if (ep == r.x && r.y == r.x) amb[atomicAdd(&namb, 1)] = tid;
-            }
+            const int4 r = rv[k];
+            const int dot = (int)(((long long)na_norm[s.x] + nb_norm[s.y] - s.z) >> 1);
+            const int ep = dot + ca[s.x];
+            keep = (ep == r.x) && (r.y < r.x);
+            if (ep == r.x && r.y == r.x) amb[atomicAdd(&namb, 1)] = tid;
         }
         keepx[tid] = keep;
         __syncthreads();
@@ -1314,6 +1432,7 @@ __global__ __launch_bounds__(256) void l2fr_final_kernel(
         base = sfm::compact256(keep, s.x, s.y, s.z, base, wsum, om, od);
     }
     if (tid == 0) out_count[p] = base;
+    }
 }
 
 // Debug dump of an intermediate record table into the match outputs (SFM_L2FR_DEBUG=1/2/3):
@@ -1366,13 +1485,12 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     const size_t rinfob = sizeof(int4) * (size_t)n_rng_max * REC_R;
     const size_t sinfob = sfm::align_up(sizeof(int4) * (size_t)n_pairs, 256);
     const size_t uinfob = sfm::align_up(UNIT * sizeof(int4) * (size_t)n_pairs, 256);
-    const size_t flagb = sfm::align_up((size_t)n_pairs, 256);  // the flags, then the pairs' smax
     // cfg4 in one launch (124 750 pairs x 4096): the two 16-byte record tables 16.4 GB (the
     // packed 8-byte forward and result records share the reverse scan's table, see below), cls
-    // 0.5 GB, the certificate's counts and flags 0.6 MB, everything else under 0.3 GB
-    char* ws = (char*)sfm::workspace(ctx, 256 + 2 * tab + 2 * recb + cntb + descb + 2 * ordb + clsb +
+    // 0.5 GB, the flagged-pair list 0.5 MB, everything else under 0.3 GB
+    char* ws = (char*)sfm::workspace(ctx, 256 + 2 * tab + 2 * recb + cntb + descb + ordb + clsb +
                                               256 + rngb + rinfob + 256 + sinfob + uinfob + 256 +
-                                              cntb + flagb + cntb);
+                                              cntb);
     if (!ws) return SFM_ERR_NOMEM;
     char* w = ws;
     uint8_t* zero_row = (uint8_t*)w; w += 256;
@@ -1381,24 +1499,22 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     int4* surv = (int4*)w; w += recb;
     int4* rev = (int4*)w; w += recb;
     // The packed forward records and the recovery's result records (8 bytes per query each) live
-    // in the two halves of the reverse scan's output table: their last reader (the certificate,
-    // or the compaction without it) is done before the reverse scan writes there.
+    // in the two halves of the reverse scan's output table: their last reader (the tail kernel)
+    // is done before the reverse scan writes there.
     rec8* fwd = (rec8*)rev;
     rec8* qst = fwd + (size_t)n_pairs * k_pad;
     int32_t* scount = (int32_t*)w; w += cntb;
     uint8_t* desc_i8 = (uint8_t*)w; w += descb;
     int32_t* ord_f = (int32_t*)w; w += ordb;
-    int32_t* ord_r = (int32_t*)w; w += ordb;
     uint8_t* cls = (uint8_t*)w; w += clsb;
-    int32_t* n_rng = (int32_t*)w; w += 256;
+    int32_t* n_rng = (int32_t*)w; w += 256;   // [0] recovery ranges, [1] flagged pairs (n_flag)
+    int32_t* n_flag = n_rng + 1;
     int2* rng = (int2*)w; w += rngb;
     int4* rinfo = (int4*)w; w += rinfob;
     int4* sinfo_f = (int4*)sfm::align_up((size_t)w, 256);
     int4* uinfo = (int4*)((char*)sinfo_f + sinfob);
     int32_t* n_units = (int32_t*)((char*)uinfo + uinfob);
-    int32_t* rcount = (int32_t*)((char*)n_units + 256);  // reverse-scan survivor counts (certificate)
-    uint8_t* flag = (uint8_t*)rcount + cntb;              // pairs the certificate left to the fallback
-    int32_t* smax = (int32_t*)(flag + flagb);             // largest survivor d1 of each pair
+    int32_t* flist = (int32_t*)((char*)n_units + 256);   // pairs left to the reverse scan
     // the forward scan by units of two pairs sharing their query image (build_units;
     // SFM_L2FR_UNITS=0: one pair per block, XCD-contiguous runs by train image)
     static const bool units_env = [] {
@@ -1413,25 +1529,21 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
     const int grid = 8 * ppx * n_qblk;
     const bool mutual = prm->cross_check == SFM_XC_MUTUAL;
 
-    const int32_t* sord_f = ord_f;
-    const int32_t* sord_r = ord_r;
-    const int unit_blk = units ? (mutual ? 2 : 1) : -1;
+    const int unit_blk = units ? 1 : -1;
     const int bpi = (k_pad + 1023) / 1024, n_prep = bpi * n_img;
-    hipLaunchKernelGGL(l2fr_setup_kernel, dim3(n_prep + (mutual ? 2 : 1) + (units ? 1 : 0)),
-                       dim3(1024), ((units ? 3 : 2) * (size_t)n_img + 2) * sizeof(int), st, n_prep,
-                       bpi, desc, n_kp, k_max, k_pad, norm, cinit, zero_row, (uint4*)desc_i8, pairs,
-                       n_pairs, n_img, ord_f, ord_r, rng, n_rng, rinfo, sinfo_f, unit_blk, uinfo,
-                       n_units);
+    hipLaunchKernelGGL(l2fr_setup_kernel, dim3(n_prep + 1 + (units ? 1 : 0)), dim3(1024),
+                       ((units ? 3 : 2) * (size_t)n_img + 2) * sizeof(int), st, n_prep, bpi, desc, n_kp,
+                       k_max, k_pad, norm, cinit, zero_row, (uint4*)desc_i8, pairs, n_pairs, n_img,
+                       ord_f, rng, n_rng, rinfo, sinfo_f, unit_blk, uinfo, n_units);
     SFM_HIP_CHECK(hipGetLastError());
     const FwdCls fc{norm, prm->ratio_num, prm->ratio_den, (long long)prm->max_dist, fwd, cls};
-    hipLaunchKernelGGL(l2fr_scan_kernel<false>, dim3(grid), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, cinit, zero_row, pairs, n_qblk, sord_f,
-                       (const int4*)(units ? uinfo : sinfo_f), n_blk, (const int4*)nullptr,
-                       (const int32_t*)nullptr, (int4*)nullptr, fc,
-                       (const int32_t*)(units ? n_units : nullptr));
+    hipLaunchKernelGGL(l2fr_scan_fwd_kernel, dim3(grid), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp, k_max,
+                       k_pad, cinit, zero_row, pairs, n_qblk, (const int4*)(units ? uinfo : sinfo_f),
+                       n_blk, fc, (const int32_t*)(units ? n_units : nullptr));
     SFM_HIP_CHECK(hipGetLastError());
     const char* dbg = getenv("SFM_L2FR_DEBUG");
-    const int dmode = dbg ? atoi(dbg) : 0;
+    int dmode = dbg ? atoi(dbg) : 0;
+    if (dmode < 1 || dmode > 3) dmode = 0;
     if (dmode == 1) {
         hipLaunchKernelGGL(l2fr_dump_kernel, dim3(n_pairs), dim3(256), 0, st, n_kp, pairs, k_max,
                            k_pad, (const int4*)nullptr, (const rec8*)fwd, (const int32_t*)nullptr,
@@ -1443,46 +1555,36 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
                        (const rec8*)fwd, (const uint8_t*)cls, prm->ratio_num, prm->ratio_den,
                        (long long)prm->max_dist, qst);
     SFM_HIP_CHECK(hipGetLastError());
-    // the ratio rule alone: the compaction writes the output itself (no final kernel)
-    const bool direct = !mutual && dmode == 0;
-    hipLaunchKernelGGL(l2fr_compact_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, norm, pairs, (const uint8_t*)cls, qst, prm->ratio_num, prm->ratio_den,
-                       (long long)prm->max_dist, surv, scount, smax,
-                       direct ? out_count : nullptr,
+    // The tail kernel: the ratio rule alone gets its output there; the mutual rule the certificate,
+    // which decides every pair it can from the forward records (it reads fwd and qst before the
+    // reverse scan overwrites the aliased rev) and lists the others for the reverse scan and the
+    // final kernel.  SFM_L2FR_CERT=0: no certificate, every pair through the reverse scan.
+    const char* ce = getenv("SFM_L2FR_CERT");
+    const bool cert = mutual && dmode == 0 && !(ce && ce[0] == '0');
+    const char* cc = getenv("SFM_L2FR_CERT_CAP");
+    const long long cap = cc ? atoll(cc) : CERT_CAP_DEFAULT;
+    unsigned long long* stats = cert && ctx->cert_stats ? ctx->cert_acc : nullptr;
+    if (stats)  // the counters are the last call's
+        SFM_HIP_CHECK(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), st));
+    auto tail = !mutual && dmode == 0 ? l2fr_tail_kernel<TAIL_DIRECT>
+                : cert                ? l2fr_tail_kernel<TAIL_CERT>
+                                      : l2fr_tail_kernel<TAIL_SPILL>;
+    hipLaunchKernelGGL(tail, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max, k_pad, norm, pairs,
+                       (const rec8*)fwd, (const uint8_t*)cls, qst, prm->ratio_num, prm->ratio_den,
+                       (long long)prm->max_dist, cap, surv, scount, flist, n_flag, stats, out_count,
                        out_match, out_dist);
     SFM_HIP_CHECK(hipGetLastError());
-    if (direct) return SFM_OK;
+    if (!mutual && dmode == 0) return SFM_OK;
     if (dmode == 2) {
         hipLaunchKernelGGL(l2fr_dump_kernel, dim3(n_pairs), dim3(256), 0, st, n_kp, pairs, k_max,
                            k_pad, (const int4*)surv, (const rec8*)nullptr, (const int32_t*)scount,
                            out_count, out_match, out_dist);
         return SFM_OK;
     }
-    // mutual rule: the certificate decides every pair it can from the forward records (it reads
-    // fwd and qst before the reverse scan overwrites the aliased rev); the reverse scan and the final
-    // kernel then see only the flagged pairs (rcount = 0 / flag = 0 elsewhere: their blocks exit
-    // at once).  SFM_L2FR_CERT=0: no certificate, every pair through the reverse scan.
-    const char* ce = getenv("SFM_L2FR_CERT");
-    const bool cert = mutual && dmode == 0 && !(ce && ce[0] == '0');
-    if (cert) {
-        const char* cc = getenv("SFM_L2FR_CERT_CAP");
-        const long long cap = cc ? atoll(cc) : CERT_CAP_DEFAULT;
-        unsigned long long* stats = ctx->cert_stats ? ctx->cert_acc : nullptr;
-        if (stats)  // the counters are the last call's
-            SFM_HIP_CHECK(hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(l2fr_mutual_cert_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp,
-                           k_max, k_pad, norm, pairs, (const rec8*)fwd, (const uint8_t*)cls,
-                           (const rec8*)qst, (const int4*)surv, (const int32_t*)scount,
-                           (const int32_t*)smax, cap, rcount, flag, stats,
-                           out_count, out_match, out_dist);
-        SFM_HIP_CHECK(hipGetLastError());
-    }
     if (mutual) {
-        hipLaunchKernelGGL(l2fr_scan_kernel<true>, dim3(grid), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp,
-                           k_max, k_pad, cinit, zero_row, pairs, n_qblk, sord_r,
-                           (const int4*)nullptr, n_blk,
-                           (const int4*)surv, (const int32_t*)(cert ? rcount : scount), rev, fc,
-                           (const int32_t*)nullptr);
+        hipLaunchKernelGGL(l2fr_scan_rev_kernel, dim3(REV_GRID), dim3(SCAN_THREADS), 0, st, desc_i8, n_kp,
+                           k_max, k_pad, cinit, zero_row, pairs, n_qblk, (const int32_t*)flist,
+                           (const int32_t*)n_flag, (const int4*)surv, (const int32_t*)scount, rev);
         SFM_HIP_CHECK(hipGetLastError());
     }
     if (dmode == 3) {
@@ -1491,12 +1593,15 @@ int sfm_match_l2fr_launch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp
                            out_count, out_match, out_dist);
         return SFM_OK;
     }
-    hipLaunchKernelGGL(l2fr_final_kernel, dim3(n_pairs), dim3(256), 0, st, desc_i8, n_kp, k_max,
-                       k_pad, norm, cinit, pairs, surv, scount, rev, mutual ? 1 : 0,
-                       (const uint8_t*)(cert ? flag : nullptr), out_count, out_match, out_dist);
+    hipLaunchKernelGGL(l2fr_final_kernel, dim3(REV_GRID), dim3(256), 0, st, desc_i8, n_kp, k_max, k_pad,
+                       norm, cinit, pairs, surv, scount, rev, (const int32_t*)flist,
+                       (const int32_t*)n_flag, out_count, out_match, out_dist);
     SFM_HIP_CHECK(hipGetLastError());
     return SFM_OK;
 }
+
+// The reverse scan's and the final kernel's grid bound (sfmcore.h).
+extern "C" int32_t sfm_l2fr_rev_grid(void) { return REV_GRID; }
 
 // Totals of the last mutual + ratio call through the certificate (sfmcore.h).
 extern "C" int sfm_match_cert_stats(sfm_ctx* ctx, int32_t enable, uint64_t* out) {

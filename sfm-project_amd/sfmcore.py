@@ -29,7 +29,7 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_graph_expand", "sfm_match_batch_both", "sfm_ransac_wave_stops",
             "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
             "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
-            "sfm_two_view_pose_batch"]
+            "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid"]
 
 
 class SfmCoreError(RuntimeError):
@@ -114,6 +114,8 @@ def load_library(path: str = LIB_PATH):
         L.sfm_ransac_stats.argtypes = [vp, i32, vp]
         L.sfm_ransac_wave_stops.argtypes = [vp, i32, i32, vp]
         L.sfm_match_cert_stats.argtypes = [vp, i32, vp]
+        L.sfm_l2fr_rev_grid.argtypes = []
+        L.sfm_l2fr_rev_grid.restype = i32
         L.sfm_calib_mfma_i8.argtypes = [vp, C.c_float, vp]
         L.sfm_ba_jtj.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, f64, vp,
                                  vp, vp, vp, vp, vp, vp]
@@ -438,6 +440,10 @@ class Context:
         _check(self.lib.sfm_match_cert_stats(self.handle, 1 if enable else 0,
                                              out if read else None))
         return (int(out[0]), int(out[1]), int(out[2])) if read else None
+
+    def l2fr_rev_grid(self):
+        """sfm_l2fr_rev_grid: the grid bound of the ratio path's reverse scan and final kernel."""
+        return int(self.lib.sfm_l2fr_rev_grid())
 
     def ransac_wave_stops(self, n_pairs, n_hyp):
         """sfm_ransac_wave_stops: [n_pairs, n_hyp / 64] u32 numpy array, the last counted batch's
