@@ -160,22 +160,26 @@ def _rotmat(r):
 
 
 def _angle_axis(R):
-    """log map, stable near 0 and π."""
+    """log map, |r| <= π (log_so3 in csrc/camera_model.h): max |rotmat(r) - R| is a few ε for
+    every angle in [0, π].  Near π (c < 0, s <= 1e-2) the axis is the largest-diagonal column of
+    S = (R + Rᵀ)/2 - c I = (1 - c) a aᵀ, which has no term in π - θ; elsewhere r = w θ / (2 s)
+    (error ε θ / s, hence the 1e-2 switch on the π side), r = w / 2 for s <= 1e-7."""
     c = np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)
     w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     s = 0.5 * np.linalg.norm(w)
     th = np.arctan2(s, c)
+    if c < 0 and s <= 1e-2:                                # th ~ π
+        S = 0.5 * (R + R.T)
+        S[np.arange(3), np.arange(3)] = np.diag(R) - c
+        d = np.diag(S)
+        j = 0 if (d[0] >= d[1] and d[0] >= d[2]) else (1 if d[1] >= d[2] else 2)
+        a = S[:, j]
+        if np.dot(a, w) < 0:
+            a = -a
+        return a * (th / np.linalg.norm(a))
     if s > 1e-7:
         return w * (th / (2.0 * s))
-    if c > 0:                                              # th ~ 0
-        return 0.5 * w
-    # th ~ π: axis from the symmetric part
-    B = 0.5 * (R + np.eye(3))
-    i = int(np.argmax(np.diag(B)))
-    a = B[:, i] / np.sqrt(B[i, i])
-    if np.dot(a, w) < 0:
-        a = -a
-    return th * a / np.linalg.norm(a)
+    return 0.5 * w                                         # th ~ 0
 
 
 def update(cams, pts, dc, dp):

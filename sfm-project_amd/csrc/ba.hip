@@ -748,29 +748,8 @@ __global__ __launch_bounds__(256) void ba_update_kernel(int n_cam, const double*
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 R[3 * r + k] = A[3 * r] * B[k] + A[3 * r + 1] * B[3 + k] + A[3 * r + 2] * B[6 + k];
-        // log map, stable near 0 and pi
-        const double cs = fmin(fmax(0.5 * ((R[0] + R[4] + R[8]) - 1.0), -1.0), 1.0);
-        const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
-        const double sn = 0.5 * sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-        const double th = atan2(sn, cs);
         double o0, o1, o2;
-        if (sn > 1e-7) {
-            const double k = th / (2.0 * sn);
-            o0 = w0 * k; o1 = w1 * k; o2 = w2 * k;
-        } else if (cs > 0.0) {
-            o0 = 0.5 * w0; o1 = 0.5 * w1; o2 = 0.5 * w2;
-        } else {  // th ~ pi: axis from the largest diagonal column of (R + I) / 2
-            const double B0 = 0.5 * (R[0] + 1.0), B4 = 0.5 * (R[4] + 1.0), B8 = 0.5 * (R[8] + 1.0);
-            const int j = (B0 >= B4 && B0 >= B8) ? 0 : (B4 >= B8 ? 1 : 2);
-            const double bjj = j == 0 ? B0 : (j == 1 ? B4 : B8);
-            const double sq = sqrt(bjj);
-            double a0 = (j == 0 ? B0 : 0.5 * R[j]) / sq;          // column j of B = (R+I)/2
-            double a1 = (j == 1 ? B4 : 0.5 * R[3 + j]) / sq;
-            double a2 = (j == 2 ? B8 : 0.5 * R[6 + j]) / sq;
-            if (a0 * w0 + a1 * w1 + a2 * w2 < 0.0) { a0 = -a0; a1 = -a1; a2 = -a2; }
-            const double n = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
-            o0 = th * a0 / n; o1 = th * a1 / n; o2 = th * a2 / n;
-        }
+        log_so3(R, o0, o1, o2);
         double* out = cams_out + 8 * (size_t)i;
         // δr = 0 exactly (a held rotation): exp(0) = I, keep r bit for bit instead of the
         // rounding of the log map of R(r)

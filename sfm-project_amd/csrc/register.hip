@@ -457,29 +457,9 @@ __global__ __launch_bounds__(256) void reg_final_kernel(
         __syncthreads();
     }
     if (tid == 0) {
-        // pose -> angle-axis (log map, stable near 0 and pi), t, f, k1
-        const double cs = fmin(fmax(0.5 * ((R[0] + R[4] + R[8]) - 1.0), -1.0), 1.0);
-        const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
-        const double sn = 0.5 * sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-        const double th = atan2(sn, cs);
+        // pose -> angle-axis (log_so3, camera_model.h), t, f, k1
         double o0, o1, o2;
-        if (sn > 1e-7) {
-            const double k = th / (2.0 * sn);
-            o0 = w0 * k; o1 = w1 * k; o2 = w2 * k;
-        } else if (cs > 0.0) {
-            o0 = 0.5 * w0; o1 = 0.5 * w1; o2 = 0.5 * w2;
-        } else {
-            const double B0 = 0.5 * (R[0] + 1.0), B4 = 0.5 * (R[4] + 1.0), B8 = 0.5 * (R[8] + 1.0);
-            const int j = (B0 >= B4 && B0 >= B8) ? 0 : (B4 >= B8 ? 1 : 2);
-            const double bjj = j == 0 ? B0 : (j == 1 ? B4 : B8);
-            const double sq = sqrt(bjj);
-            double a0 = (j == 0 ? B0 : 0.5 * R[j]) / sq;
-            double a1 = (j == 1 ? B4 : 0.5 * R[3 + j]) / sq;
-            double a2 = (j == 2 ? B8 : 0.5 * R[6 + j]) / sq;
-            if (a0 * w0 + a1 * w1 + a2 * w2 < 0.0) { a0 = -a0; a1 = -a1; a2 = -a2; }
-            const double nn = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
-            o0 = th * a0 / nn; o1 = th * a1 / nn; o2 = th * a2 / nn;
-        }
+        log_so3(R, o0, o1, o2);
         double* out = cam_out + 8 * (size_t)im;
         out[0] = o0; out[1] = o1; out[2] = o2;
         out[3] = t[0]; out[4] = t[1]; out[5] = t[2];

@@ -131,6 +131,31 @@ def test_update_matches_oracle():
     np.testing.assert_allclose(po, op, rtol=0, atol=0)
 
 
+def test_update_at_the_half_turn_matches_50_digits():
+    """Compositions that land at pi -+ delta (delta from 0 to 3e-2, about e_x, e_y, e_z and three
+    random axes: every branch of log_so3 and every column choice) against the 50-digit product of
+    the two rotations formed from the float inputs; and delta_r = 0 keeps r bit for bit there."""
+    import torch
+    import hp_ref
+    import recon_edge_cases as E
+    cams, dc, ref = E.half_turn_update()
+    hold = dc.copy()
+    hold[:, :3] = 0.0
+    cams2, dc2 = np.concatenate([cams, cams]), np.concatenate([dc, hold])
+    assert len(cams2) > 256                              # more than one block
+    ctx = R.sfmcore.context(0)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()
+    pts = np.zeros((1, 3))
+    co, _ = (t.cpu().numpy() for t in ctx.ba_update(T(cams2), T(dc2), T(pts), T(pts)))
+    n = len(cams)
+    errs = [hp_ref.rot_err(co[c, :3], ref[c]) for c in range(n)]
+    print(f"update at pi -+ delta: worst {max(errs):.3g}")
+    assert max(errs) <= E.LOGMAP_TOL
+    assert np.linalg.norm(co[:n, :3], axis=1).max() <= np.pi + 1e-12
+    np.testing.assert_array_equal(co[:, 3:], cams2[:, 3:] + dc2[:, 3:])
+    np.testing.assert_array_equal(co[n:, :3], cams[:, :3])
+
+
 def test_bundle_adjust_matches_scipy_and_oracle():
     from test_ba_lm_cpu import _scipy_solution
     prob = synth.make_ba_problem(6, 120, obs_per_pt=4, seed=3, perturb=2e-3)

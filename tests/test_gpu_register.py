@@ -73,3 +73,74 @@ def test_register_failures_and_batch_invariance():
     assert cnt1[0] == cnt[1] and key1[0] == key[1]
     np.testing.assert_array_equal(cams1[0], cams[1])
     np.testing.assert_array_equal(mask1, mask[2:])
+
+
+def _oracle(im, img):
+    import recon_edge_cases as E
+    return O.reg_ransac(im["xy"], im["X"], im["intr"], img=img, n_hyp=E.REG_N_HYP, seed=E.REG_SEED,
+                        thr=E.REG_THR)
+
+
+def test_register_rotations_at_zero_and_the_half_turn():
+    """True rotations I, exp(3e-9 a) and half turns less 1e-8 / 3e-7 about e_x, e_y, e_z and a
+    random axis (noise-free inliers, 30 % outliers): the RANSAC part bit-identical, the unrefined
+    pose's angle-axis within 1e-12 of the oracle's rotation matrix (50-digit rotmat), the refined
+    one within 1e-9 of the numpy Gauss-Newton restatement."""
+    import hp_ref
+    import recon_edge_cases as E
+    images = E.reg_pose_images()
+    ids = np.arange(len(images), dtype=np.int32) + 2
+    kw = dict(n_hyp=E.REG_N_HYP, thr=E.REG_THR)
+    raw, cnt, key, mask, ptr = _gpu(images, ids, refine=False, **kw)
+    ref, cnt2, key2, mask2, _ = _gpu(images, ids, refine=True, **kw)
+    np.testing.assert_array_equal(cnt, cnt2)
+    np.testing.assert_array_equal(key, key2)
+    np.testing.assert_array_equal(mask, mask2)
+    sines = []
+    for i, im in enumerate(images):
+        o = _oracle(im, int(ids[i]))
+        assert cnt[i] == o["count"] and key[i] == o["key"] and o["count"] >= 100
+        np.testing.assert_array_equal(mask[ptr[i]:ptr[i + 1]], o["mask"])
+        w = np.array([o["R"][2, 1] - o["R"][1, 2], o["R"][0, 2] - o["R"][2, 0],
+                      o["R"][1, 0] - o["R"][0, 1]])
+        sines.append(0.5 * np.linalg.norm(w))
+        err = hp_ref.rot_err(raw[i, :3], [[hp_ref.mp.mpf(float(x)) for x in row] for row in o["R"]])
+        assert err <= E.LOGMAP_TOL, (i, err)
+        assert np.linalg.norm(raw[i, :3]) <= np.pi + 1e-12
+        np.testing.assert_array_equal(raw[i, 3:6], o["t"])
+        np.testing.assert_array_equal(raw[i, 6:], im["intr"][:2])
+        Rr, tr = recon.reg_refine(o["R"], o["t"], im["xy"], im["X"], im["intr"], o["mask"])
+        np.testing.assert_allclose(recon._rotmat(ref[i, :3]), Rr, atol=1e-9)
+        np.testing.assert_allclose(ref[i, 3:6], tr, rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(Rr, im["R"], atol=1e-6)
+    print("sin(theta) of the RANSAC rotations:", " ".join(f"{s:.1e}" for s in sines))
+    assert min(sines) < 1e-7 and max(sines) > 1e-7       # both sides of the near-0 / near-pi switch
+
+
+def test_register_degenerate_and_small_inside_a_batch():
+    """Collinear and coincident 3-D points (n >= 3 but no valid hypothesis), planar structure,
+    n = 3 and n = 4, between good images of one batch: counts, keys and masks as the oracle's,
+    failures zeroed, and the good images as when registered alone."""
+    import recon_edge_cases as E
+    kinds, images = zip(*E.reg_degenerate_images())
+    ids = np.arange(len(images), dtype=np.int32) + 1
+    kw = dict(n_hyp=E.REG_N_HYP, thr=E.REG_THR)
+    cams, cnt, key, mask, ptr = _gpu(list(images), ids, **kw)
+    for i, (kind, im) in enumerate(zip(kinds, images)):
+        o = _oracle(im, int(ids[i]))
+        assert cnt[i] == o["count"] and key[i] == o["key"], (kind, cnt[i], key[i], o)
+        m = mask[ptr[i]:ptr[i + 1]]
+        if kind in ("collinear", "coincident"):
+            assert cnt[i] == -1 and key[i] == -1 and np.all(cams[i] == 0) and not m.any()
+            continue
+        np.testing.assert_array_equal(m, o["mask"])
+        assert cnt[i] >= min(len(im["xy"]), 50) * 0.6, (kind, cnt[i])
+        Rr, tr = recon.reg_refine(o["R"], o["t"], im["xy"], im["X"], im["intr"], o["mask"])
+        np.testing.assert_allclose(recon._rotmat(cams[i, :3]), Rr, atol=1e-9)
+        np.testing.assert_allclose(cams[i, 3:6], tr, rtol=1e-9, atol=1e-9)
+    good = [i for i, k in enumerate(kinds) if k == "good"]
+    alone = _gpu([images[i] for i in good], ids[good], **kw)
+    np.testing.assert_array_equal(alone[0], cams[good])
+    np.testing.assert_array_equal(alone[1], cnt[good])
+    np.testing.assert_array_equal(alone[2], key[good])
+    np.testing.assert_array_equal(alone[3], np.concatenate([mask[ptr[i]:ptr[i + 1]] for i in good]))
