@@ -3,9 +3,11 @@
 // Fills the empty reference module code/geometric_verification.py (placeholder at
 // code/pipeline.py:60).  Default schedule (SFM_RANSAC_MODE 0, "ordered"; described above
 // ransac_fit_kernel): ransac_prep -> ransac_fit (sample, fit, 64-match preview, one 48-byte record
-// per hypothesis) -> ransac_order (per-pair sort by preview) -> ransac_score (pruned scoring in
-// preview order; an XCD's pairs in groups, hb-major inside a group, xcd_pair_block) ->
-// ransac_final.  The single-pass schedules (modes 1, 2) use three kernels per batch of pairs:
+// per hypothesis) -> ransac_order (per-pair sort by preview) -> ransac_score twice (pruned scoring
+// in preview order: first one pilot wave per pair, the 64 best-previewed hypotheses, then every
+// other wave with the pilot's bound; an XCD's pairs in groups, hb-major inside a group,
+// xcd_pair_block) -> ransac_final.  The single-pass schedules (modes 1, 2) use three kernels per
+// batch of pairs:
 //   ransac_prep   one wave per pair: gathers the tentative-match pixel coordinates, Hartley-
 //                 normalises each side with a fixed-order wave reduction and writes 8 planes per
 //                 pair: the normalised x1|y1|x2|y2 (fits) and the Sampson-scaled X1|Y1|X2|Y2
@@ -265,8 +267,9 @@ __global__ __launch_bounds__(256) void ransac_hyp_kernel(
 //   ransac_order_kernel  block per pair: counting sort of the hypotheses by preview count,
 //                        descending (order within a bucket is irrelevant: the winner key carries h).
 //   ransac_score_kernel  rank r of pair p scores hypothesis order[p][r] from match PV on, starting
-//                        from its preview count, with the same exact pruning; grid x = pair so the
-//                        best-previewed block of every pair runs first and publishes a strong bound.
+//                        from its preview count, with the same exact pruning; launched twice: the
+//                        pilot wave of every pair (ranks 0..63) first, so that every other wave
+//                        starts with a strong bound (measured: profiles/k2_pilot/README.md).
 // PV = 128: interleaved A/B at cfg4 (profiles/r04/ransac_preview_ab_r6i.txt, _r6j.txt): 32 206.5,
 // 64 202.2, 96 200.7, 128 199.7 ms; second box 64 207.0-207.6 vs 128-224 a plateau at 204.3-205.2;
 // cfg3 within noise, outputs identical.  (hist[PV + 2] in 256 threads: PV <= 240, multiple of 16.)
@@ -286,6 +289,14 @@ __device__ __forceinline__ bool score_matches(typename CPtr<T>::type S, int kp, 
                                               const unsigned long long* __restrict__ bestp,
                                               int* mstop = nullptr) {
     const int mc = m + ((mend - m) & ~(C - 1));
+    // The published bound is read one prune period ahead of its use (the homography path's form,
+    // ransac_h.hip): a stale value is still a lower bound on the winning count (best[p] only
+    // grows), and the load's latency hides behind a period's arithmetic instead of stalling the
+    // wave at every check.  Only the key's high word (count + 1) is read: it never decreases
+    // either, and a one-register destination keeps the load in flight across the period.
+    [[maybe_unused]] const unsigned* best_hi = PRUNE ? (const unsigned*)bestp + 1 : nullptr;
+    [[maybe_unused]] unsigned bhi = 0;
+    if constexpr (PRUNE) bhi = __hip_atomic_load(best_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll 1
     for (; m < mc; m += C) {
         T x1[C], y1[C], x2[C], y2[C];
@@ -305,13 +316,18 @@ __device__ __forceinline__ bool score_matches(typename CPtr<T>::type S, int kp, 
 #pragma unroll
             for (int j = 0; j < C; ++j) cnt += sampson_inlier(G, x1[j], y1[j], x2[j], y2[j]);
         }
-        if (PRUNE && ((m + C) % PRUNE_EVERY) == 0) {
-            const unsigned long long bk =
-                __hip_atomic_load(bestp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int bound = (int)(bk >> 32) - 1;
-            if (__all(cnt + (M - m - C) < bound)) {
-                if (mstop) *mstop = m + C;
-                return false;
+        if constexpr (PRUNE) {
+            if (((m + C) % PRUNE_EVERY) == 0) {
+                // Exact pruning: every key in best[p] is a real hypothesis's final (count, h), so
+                // (high word) - 1, however stale or early (a pilot wave's), is a lower bound on
+                // the winning count.  The stop rule is strict: a lane that can still TIE the
+                // bound is scored to the end, and the lowest h among the tied wins the atomicMax.
+                const int bound = (int)bhi - 1;
+                if (__all(cnt + (M - m - C) < bound)) {
+                    if (mstop) *mstop = m + C;
+                    return false;
+                }
+                bhi = __hip_atomic_load(best_hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -409,14 +425,30 @@ __global__ __launch_bounds__(256) void ransac_order_kernel(int n_hyp,
 }
 
 // COUNTS: no pruning; every hypothesis's count to out_counts[p][h] (sfm_ransac_counts)
+//
+// Rank window [r_lo, r_hi) (multiples of 64) over a grid of n_hb hypothesis blocks per pair: a
+// wave whose first rank lies outside the window returns before its first load (wave-uniform; the
+// kernel has no barrier).  The ordered schedule scores every pair's PILOT wave first (ransac_batch:
+// ranks [0, 64), the 64 best-previewed hypotheses, one 64-thread block per pair, n_hb = 1) and
+// then the rest in a second launch, so every other wave starts with a bound instead of running
+// most of its sweep before its pair's first block has published anything.  Every wave is scored
+// by exactly one of the two launches (one exec_w store per wave).
+// Results cannot change: every key in best[p] is still a real hypothesis's final (count, h) —
+// nothing publishes a running count, degenerate hypotheses publish -1 as before — so whenever a
+// bound is read, early (the pilot's) or stale (one period old, score_matches), it is a lower
+// bound on the winning count; the stop rule stays strict (cnt + remaining < bound), so a
+// hypothesis that can still tie the bound is scored to the end and lowest h decides.
 template <typename T, bool PRUNE, bool COUNTS = false>
 __global__ __launch_bounds__(256) void ransac_score_kernel(
     int n_pairs, int k_max, const int32_t* __restrict__ match_count,
-    const T* __restrict__ planes, int n_hyp, int gp, const T* __restrict__ hypG,
-    const uint16_t* __restrict__ order, unsigned long long* __restrict__ best, int32_t* __restrict__ out_counts = nullptr,
+    const T* __restrict__ planes, int n_hyp, int n_hb, int gp, int r_lo, int r_hi,
+    const T* __restrict__ hypG, const uint16_t* __restrict__ order,
+    unsigned long long* __restrict__ best, int32_t* __restrict__ out_counts = nullptr,
     uint32_t* __restrict__ exec_w = nullptr) {
     int p, hb;
-    if (!xcd_pair_block(n_pairs, n_hyp >> 8, gp, p, hb)) return;
+    if (!xcd_pair_block(n_pairs, n_hb, gp, p, hb)) return;
+    const int wr = __builtin_amdgcn_readfirstlane(hb * 256 + (int)(threadIdx.x & ~63u));
+    if (wr < r_lo || wr >= r_hi) return;  // wave-uniform: the other launch scores this wave
     const int M = match_count[p];
     if (M < 8) return;  // block-uniform
     const int kp = plane_len(k_max);
@@ -568,6 +600,15 @@ static int ransac_mode() {
     return (v < 0 || v > 2) ? 0 : v;
 }
 
+// Ranks of the ordered schedule's pilot launch (ransac_score_kernel): 64 = one wave per pair
+// (default), 256 = the pair's first block, 0 = one launch without a pilot.  SFM_RANSAC_PILOT
+// overrides (A/B only; same results at every value).
+static int ransac_pilot() {
+    const char* e = getenv("SFM_RANSAC_PILOT");
+    const int v = e ? atoi(e) : 64;
+    return (v < 0 || v > 256 || v % 64 != 0) ? 64 : v;
+}
+
 namespace {
 struct RansacWs {
     void* planes;
@@ -636,9 +677,18 @@ static int ransac_batch(sfm_ctx* ctx, const T* kps, int32_t k_max, const int32_t
         hipLaunchKernelGGL(ransac_order_kernel, dim3(n_pairs), dim3(256), 0, st, H, match_count,
                            w.prev, w.order);
         SFM_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL((ransac_score_kernel<T, true>), xgrid, dim3(256), 0, st, n_pairs, k_max,
-                           match_count, planes, H, gp, hypG, w.order, w.best, (int32_t*)nullptr,
-                           exec_w);
+        // pilot wave(s) of every pair first (ransac_score_kernel), then the rest with that bound
+        const int pilot = ransac_pilot();
+        if (pilot > 0) {
+            hipLaunchKernelGGL((ransac_score_kernel<T, true>), dim3(xcd_grid(n_pairs, 1)),
+                               dim3(pilot), 0, st, n_pairs, k_max, match_count, planes, H, 1, gp, 0,
+                               pilot, hypG, w.order, w.best, (int32_t*)nullptr, exec_w);
+            SFM_HIP_CHECK(hipGetLastError());
+        }
+        if (pilot < H)
+            hipLaunchKernelGGL((ransac_score_kernel<T, true>), xgrid, dim3(256), 0, st, n_pairs,
+                               k_max, match_count, planes, H, H / 256, gp, pilot, H, hypG, w.order,
+                               w.best, (int32_t*)nullptr, exec_w);
         if (exec_w) {
             SFM_HIP_CHECK(hipGetLastError());
             hipLaunchKernelGGL(ransac_stats_kernel, dim3(std::min((n_pairs + 3) / 4, 512)),
@@ -721,8 +771,8 @@ extern "C" int sfm_ransac_counts(sfm_ctx* ctx, const float* kps, int32_t n_img, 
                        w.prev, w.order);
     SFM_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((ransac_score_kernel<float, false, true>), xgrid, dim3(256), 0, st,
-                       n_pairs, k_max, match_count, planes, H, gp, hypG, w.order, w.best,
-                       out_counts, (uint32_t*)nullptr);
+                       n_pairs, k_max, match_count, planes, H, H / 256, gp, 0, H, hypG, w.order,
+                       w.best, out_counts, (uint32_t*)nullptr);
     SFM_HIP_CHECK(hipGetLastError());
     if (out_hyp_mask) {
         hipLaunchKernelGGL(ransac_hyp_mask_kernel, dim3(n_pairs, H / 256), dim3(256), 0, st, k_max,
