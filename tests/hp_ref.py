@@ -1,8 +1,8 @@
 """50-digit references for the steps after the match graph (test infrastructure, mpmath).
 
-Written from the specs in the kernel headers (csrc/camera_model.h, csrc/triangulate.hip), not from
-the kernels: every quantity is formed in 50-digit arithmetic from the float64 inputs, so the only
-error a comparison charges to the code under test is its own.
+Written from the specs in the kernel headers (csrc/camera_model.h, csrc/triangulate.hip,
+csrc/ba.hip), not from the kernels: every quantity is formed in 50-digit arithmetic from the
+float64 inputs, so the only error a comparison charges to the code under test is its own.
 
   rotmat(r)                                   Rodrigues; the spec's first-order form for |r|^2 <= 1e-20
   rot_err(r_out, R_ref)                       max |rotmat(r_out) - R_ref|
@@ -10,6 +10,12 @@ error a comparison charges to the code under test is its own.
   triangulate(cams, pp, pt_ptr, cam_idx, uv)  multi-view DLT, statistics, status, eigenvalues
   stats_f64(...)                              the three statistics at a given X, float64 (for
                                               propagating a point tolerance to the statistics)
+  ba_obs(cam, pp, X, uv, loss_s)              one BA observation: residual, 2x11 Jacobian by central
+                                              differences in 50 digits, Cauchy w and rho
+  ba_assemble(...)                            the whole linearisation summed in 50 digits, with units
+  ba_residuals(...)                           residuals, rho and the cost alone (large problems)
+  ba_f64(...), ba_units(...)                  float64 restatement of the linearisation carrying a
+                                              first-order error unit for every entry
 """
 from __future__ import annotations
 
@@ -191,3 +197,339 @@ def _cached_R_key(key):
 
 def _cached_R(r):
     return _cached_R_key(tuple(float(x) for x in r))
+
+
+# ---- bundle-adjustment linearisation --------------------------------------------------------------
+# Spec (headers of csrc/camera_model.h and csrc/ba.hip): r = f (1 + k1 |p|^2) p + pp - uv,
+# p = (P0/P2, P1/P2), P = rotmat(r) X + t; e = |r|^2; Cauchy w = 1 / (1 + e/s^2),
+# rho = s^2 log1p(e/s^2) for loss_s > 0, else w = 1, rho = e.  The Jacobian's 11 columns follow the
+# increment ba_update_kernel applies: R <- exp([d]x) R (3), then t (3), f, k1 and X (3) additive.
+
+FD_STEP = "1e-17"          # central differences in 50 digits: good to ~30 digits
+EPS = float(np.finfo(np.float64).eps)
+BA_OUTPUTS = ("res", "W", "U", "V", "gc", "gp", "cost")
+
+
+@functools.lru_cache(maxsize=None)
+def _increments():
+    """(h, [exp(+h e_k)], [exp(-h e_k)]): the six rotation increments, formed once."""
+    with mp.workdps(DPS):
+        h = mp.mpf(FD_STEP)
+        ax = ((1, 0, 0), (0, 1, 0), (0, 0, 1))
+        return h, [exp_so3(a, h) for a in ax], [exp_so3(a, -h) for a in ax]
+
+
+def _residual(R, t, f, k1, X, c_pp, m):
+    P = [R[i][0] * X[0] + R[i][1] * X[1] + R[i][2] * X[2] + t[i] for i in range(3)]
+    p0, p1 = P[0] / P[2], P[1] / P[2]
+    d = 1 + k1 * (p0 * p0 + p1 * p1)
+    return [f * d * p0 + c_pp[0] - m[0], f * d * p1 + c_pp[1] - m[1]], P
+
+
+@functools.lru_cache(maxsize=None)
+def _ba_obs_geom(key):
+    """(residual [2], Jacobian 2x11, P) of one observation in 50 digits; key = the 15 float64
+    inputs (cam 8, pp 2, X 3, uv 2).  Cached: the loss does not enter."""
+    with mp.workdps(DPS):
+        v = [mp.mpf(x) for x in key]
+        R, t, f, k1 = rotmat(v[0:3]), v[3:6], v[6], v[7]
+        c_pp, X, m = v[8:10], v[10:13], v[13:15]
+        h, Ep, Em = _increments()
+        r0, P = _residual(R, t, f, k1, X, c_pp, m)
+        J = [[None] * 11, [None] * 11]
+
+        def put(col, plus, minus):
+            for a in range(2):
+                J[a][col] = (plus[a] - minus[a]) / (2 * h)
+
+        def bump(vec, k, s):
+            return [x + s * h if i == k else x for i, x in enumerate(vec)]
+
+        for k in range(3):
+            put(k, _residual(matmul(Ep[k], R), t, f, k1, X, c_pp, m)[0],
+                _residual(matmul(Em[k], R), t, f, k1, X, c_pp, m)[0])
+            put(3 + k, _residual(R, bump(t, k, 1), f, k1, X, c_pp, m)[0],
+                _residual(R, bump(t, k, -1), f, k1, X, c_pp, m)[0])
+            put(8 + k, _residual(R, t, f, k1, bump(X, k, 1), c_pp, m)[0],
+                _residual(R, t, f, k1, bump(X, k, -1), c_pp, m)[0])
+        put(6, _residual(R, t, f + h, k1, X, c_pp, m)[0], _residual(R, t, f - h, k1, X, c_pp, m)[0])
+        put(7, _residual(R, t, f, k1 + h, X, c_pp, m)[0], _residual(R, t, f, k1 - h, X, c_pp, m)[0])
+        return r0, J, P
+
+
+def _obs_key(cam, pp, X, uv):
+    return tuple(float(x) for x in (*cam, *pp, *X, *uv))
+
+
+def _loss_terms(r, loss_s):
+    e = r[0] * r[0] + r[1] * r[1]
+    if loss_s > 0:
+        s2 = mp.mpf(float(loss_s)) ** 2
+        return e, 1 / (1 + e / s2), s2 * mp.log1p(e / s2)
+    return e, mp.mpf(1), e
+
+
+@_hp
+def ba_obs(cam, pp, X, uv, loss_s=0.0):
+    """One observation in 50 digits on the float64 inputs: dict of mpf r [2], J [2][11] (central
+    differences of the residual, no analytic formula), P [3], e, w, rho."""
+    r, J, P = _ba_obs_geom(_obs_key(cam, pp, X, uv))
+    e, w, rho = _loss_terms(r, loss_s)
+    return dict(r=r, J=J, P=P, e=e, w=w, rho=rho)
+
+
+@_hp
+def ba_residuals(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0):
+    """res [n,2], rho [n] as float64 and cost = sum rho / 2 (summed in 50 digits): the residual
+    alone, for problems too large for the finite-difference Jacobian."""
+    n = len(cam_idx)
+    res, rho, cost = np.zeros((n, 2)), np.zeros(n), mp.mpf(0)
+    rot = {}
+    for o in range(n):
+        c, p = int(cam_idx[o]), int(pt_idx[o])
+        if c not in rot:
+            rot[c] = rotmat(cams[c, :3])
+        cam = _vec(cams[c])
+        r, _ = _residual(rot[c], cam[3:6], cam[6], cam[7], _vec(pts[p]), _vec(pp[c]), _vec(uv[o]))
+        _, _, rh = _loss_terms(r, loss_s)
+        res[o], rho[o] = [float(x) for x in r], float(rh)
+        cost += rh / 2
+    return res, rho, float(cost)
+
+
+@_hp
+def ba_assemble(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0):
+    """The linearisation of a whole problem, every product and sum in 50 digits, returned as
+    float64: res [n,2], W [n,8,3] = w Jc^T Jp, U [n_cam,8,8] = sum w Jc^T Jc and gc [n_cam,8] =
+    sum w Jc^T r over each camera's observations, V [n_pt,3,3], gp [n_pt,3] over each point's,
+    cost = sum rho / 2, J [n,2,11], w [n], rho [n]; and "unit": the tolerance unit of every entry
+    of the seven outputs (ba_units)."""
+    cams, pp, pts, uv = (np.asarray(a, np.float64) for a in (cams, pp, pts, uv))
+    n, nc, npt = len(cam_idx), len(cams), len(pts)
+    zero = mp.mpf(0)
+    U = [[[zero] * 8 for _ in range(8)] for _ in range(nc)]
+    gc = [[zero] * 8 for _ in range(nc)]
+    V = [[[zero] * 3 for _ in range(3)] for _ in range(npt)]
+    gp = [[zero] * 3 for _ in range(npt)]
+    out = dict(res=np.zeros((n, 2)), W=np.zeros((n, 8, 3)), J=np.zeros((n, 2, 11)), w=np.zeros(n),
+               rho=np.zeros(n))
+    cost = zero
+    for o in range(n):
+        c, p = int(cam_idx[o]), int(pt_idx[o])
+        q = ba_obs(cams[c], pp[c], pts[p], uv[o], loss_s)
+        r, J, w = q["r"], q["J"], q["w"]
+        Jc = [J[0][:8], J[1][:8]]
+        Jp = [J[0][8:], J[1][8:]]
+        cost += q["rho"] / 2
+        out["res"][o] = [float(x) for x in r]
+        out["J"][o] = [[float(x) for x in row] for row in J]
+        out["w"][o], out["rho"][o] = float(w), float(q["rho"])
+        for i in range(8):
+            for j in range(i, 8):
+                U[c][i][j] += w * (Jc[0][i] * Jc[0][j] + Jc[1][i] * Jc[1][j])
+            gc[c][i] += w * (Jc[0][i] * r[0] + Jc[1][i] * r[1])
+            for j in range(3):
+                out["W"][o, i, j] = float(w * (Jc[0][i] * Jp[0][j] + Jc[1][i] * Jp[1][j]))
+        for i in range(3):
+            for j in range(i, 3):
+                V[p][i][j] += w * (Jp[0][i] * Jp[0][j] + Jp[1][i] * Jp[1][j])
+            gp[p][i] += w * (Jp[0][i] * r[0] + Jp[1][i] * r[1])
+    sym = lambda M, k: np.array([[[float(B[min(i, j)][max(i, j)]) for j in range(k)]
+                                  for i in range(k)] for B in M]).reshape(len(M), k, k)
+    out.update(U=sym(U, 8), V=sym(V, 3), cost=float(cost),
+               gc=np.array([[float(x) for x in g] for g in gc]).reshape(nc, 8),
+               gp=np.array([[float(x) for x in g] for g in gp]).reshape(npt, 3))
+    out["unit"] = ba_units(cams, pp, pts, cam_idx, pt_idx, uv, loss_s)
+    return out
+
+
+# ---- float64 restatement with first-order error units ---------------------------------------------
+# Every quantity is a (value, unit) pair of numpy arrays over the observations.  The value is the
+# float64 restatement; the unit is the first-order propagation of a relative eps on t, X, f, k1, pp
+# and uv and an absolute eps on the entries of R, plus eps |q| per operation:
+#   u(a b) = |a| u(b) + |b| u(a) + eps |a b|,   u(sum) = sum u + eps sum |term|.
+
+class VU:
+    __slots__ = ("v", "u")
+
+    def __init__(self, v, u=None):
+        self.v = np.asarray(v, np.float64)
+        self.u = np.zeros_like(self.v) if u is None else np.asarray(u, np.float64)
+
+    @staticmethod
+    def rel(x):
+        return VU(x, EPS * np.abs(x))
+
+    @staticmethod
+    def absolute(x):
+        x = np.asarray(x, np.float64)
+        return VU(x, np.full_like(x, EPS))
+
+    def __mul__(self, o):
+        v = self.v * o.v
+        return VU(v, np.abs(self.v) * o.u + np.abs(o.v) * self.u + EPS * np.abs(v))
+
+    def __truediv__(self, o):
+        v = self.v / o.v
+        return VU(v, self.u / np.abs(o.v) + np.abs(v) * o.u / np.abs(o.v) + EPS * np.abs(v))
+
+    def __neg__(self):
+        return VU(-self.v, self.u)
+
+    def scale(self, k):
+        """Times a power of two: exact."""
+        return VU(self.v * k, self.u * abs(k))
+
+
+def vsum(terms):
+    """Left-to-right float64 sum; unit sum u + eps sum |term|."""
+    v, u, a = terms[0].v, terms[0].u, np.abs(terms[0].v)
+    for t in terms[1:]:
+        v, u, a = v + t.v, u + t.u, a + np.abs(t.v)
+    return VU(v, u + EPS * a)
+
+
+def _log1p(x):
+    v = np.log1p(x.v)
+    return VU(v, x.u / np.abs(1.0 + x.v) + EPS * np.abs(v))
+
+
+def rotmat_f64(r, mut=""):
+    """[n,3,3] float64 Rodrigues of r [n,3] (numpy), first-order form for |r|^2 <= 1e-20.
+    Mutations: "e" first-order form up to 1e-12, "f" sin / cos rounded to float32."""
+    r = np.asarray(r, np.float64).reshape(-1, 3)
+    th2 = (r * r).sum(1)
+    small = th2 <= (1e-12 if mut == "e" else 1e-20)
+    th = np.sqrt(np.where(small, 1.0, th2))
+    s, c = np.sin(th), np.cos(th)
+    if mut == "f":
+        s, c = s.astype(np.float32).astype(np.float64), c.astype(np.float32).astype(np.float64)
+    a = r / th[:, None]
+    K = np.zeros((len(r), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 2] = -a[:, 2], a[:, 1], -a[:, 0]
+    K -= K.transpose(0, 2, 1)
+    full = (c[:, None, None] * np.eye(3) + (1.0 - c)[:, None, None] * a[:, :, None] * a[:, None, :]
+            + s[:, None, None] * K)
+    K1 = np.zeros_like(K)
+    K1[:, 0, 1], K1[:, 0, 2], K1[:, 1, 2] = -r[:, 2], r[:, 1], -r[:, 0]
+    K1 -= K1.transpose(0, 2, 1)
+    return np.where(small[:, None, None], np.eye(3) + K1, full)
+
+
+def ba_terms_f64(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0, mut=""):
+    """The per-observation quantities of the linearisation as VU pairs (chain rule written from
+    the spec): dict of res [2], J [2][11], w, rho, hrho (= rho / 2) and the summands W [8][3],
+    U [8][8], gc [8], V [3][3], gp [3].  mut: one of the mutations a-f, h of the mutation check
+    (tests/test_ba_hp_cpu.py); never set otherwise."""
+    cams, pp, pts, uv = (np.asarray(a, np.float64) for a in (cams, pp, pts, uv))
+    ci, pi = np.asarray(cam_idx, np.int64), np.asarray(pt_idx, np.int64)
+    Rn = rotmat_f64(cams[:, :3], mut)[ci]
+    R = [[VU.absolute(Rn[:, i, j]) for j in range(3)] for i in range(3)]
+    X = [VU.rel(pts[pi, j]) for j in range(3)]
+    t = [VU.rel(cams[ci, 3 + j]) for j in range(3)]
+    f, k1 = VU.rel(cams[ci, 6]), VU.rel(cams[ci, 7])
+    c_pp = [VU.rel(pp[ci, a]) for a in range(2)]
+    m = [VU.rel(uv[:, a]) for a in range(2)]
+    one = VU(np.ones(len(ci)))
+    Y = [vsum([R[i][j] * X[j] for j in range(3)]) for i in range(3)]
+    P = [vsum([R[i][j] * X[j] for j in range(3)] + [t[i]]) for i in range(3)]
+    p = [P[0] / P[2], P[1] / P[2]]
+    q = vsum([p[0] * p[0], p[1] * p[1]])
+    d = vsum([one, k1 * q])
+    fd = f * d
+    res = [vsum([fd * p[a], c_pp[a], -m[a]]) for a in range(2)]
+    e = vsum([res[0] * res[0], res[1] * res[1]])
+    if loss_s > 0:
+        s2 = VU.rel(np.full(len(ci), float(loss_s) * float(loss_s)))
+        x = e / (VU.rel(np.full(len(ci), float(loss_s))) if mut == "d" else s2)
+        w = one / vsum([one, x])
+        rho = s2 * (VU(np.log(1.0 + x.v), _log1p(x).u) if mut == "h" else _log1p(x))
+    else:
+        w, rho = one, e
+    # M = d pred / d p, D = d p / d P, A = M D
+    cross = (k1 * p[0] * p[1]).scale(1.0 if mut == "a" else 2.0)
+    M = [[f * vsum([d, (k1 * p[0] * p[0]).scale(2.0)]), f * cross],
+         [f * cross, f * vsum([d, (k1 * p[1] * p[1]).scale(2.0)])]]
+    iz = one / P[2]
+    A = [[M[a][0] * iz, M[a][1] * iz, -(vsum([M[a][0] * p[0], M[a][1] * p[1]]) * iz)]
+         for a in range(2)]
+    # d P / d delta = -[Y]x: column j is e_j x Y
+    sgn = -1.0 if mut == "b" else 1.0
+    J = [[vsum([-(A[a][1] * Y[2]), A[a][2] * Y[1]]),
+          vsum([(A[a][0] * Y[2]).scale(sgn), -(A[a][2] * Y[0])]),
+          vsum([-(A[a][0] * Y[1]), A[a][1] * Y[0]]),
+          A[a][0], A[a][1], A[a][2],
+          d * p[a], (q * p[a]) if mut == "c" else (f * q * p[a])]
+         + [vsum([A[a][k] * R[k][j] for k in range(3)]) for j in range(3)] for a in range(2)]
+    Jc, Jp = [J[0][:8], J[1][:8]], [J[0][8:], J[1][8:]]
+    jtj = lambda Ja, i, Jb, j: w * vsum([Ja[0][i] * Jb[0][j], Ja[1][i] * Jb[1][j]])
+    jtr = lambda Ja, i: w * vsum([Ja[0][i] * res[0], Ja[1][i] * res[1]])
+    return dict(res=res, J=J, w=w, rho=rho, hrho=rho.scale(0.5),
+                W=[[jtj(Jc, i, Jp, j) for j in range(3)] for i in range(8)],
+                U=[[jtj(Jc, min(i, j), Jc, max(i, j)) for j in range(8)] for i in range(8)],
+                gc=[jtr(Jc, i) for i in range(8)],
+                V=[[jtj(Jp, min(i, j), Jp, max(i, j)) for j in range(3)] for i in range(3)],
+                gp=[jtr(Jp, i) for i in range(3)])
+
+
+def _stack(x, field):
+    """Nested lists of VU -> array [n, ...] of the values or the units."""
+    if isinstance(x, VU):
+        return getattr(x, field)
+    return np.stack([_stack(y, field) for y in x], axis=-1) if isinstance(x[0], VU) else \
+        np.stack([_stack(y, field) for y in x], axis=-2)
+
+
+def _segment(terms, index, n, exact=False, drop=None):
+    """Sums of the summands `terms` (nested VU) over equal `index`: (values [n, ...], units).
+    Values: numpy's sequential sum, or math.fsum of the float64 summands (exact=True).
+    drop: an observation left out of the value (mutation g)."""
+    import math
+    v, u = _stack(terms, "v"), _stack(terms, "u")
+    keep = np.ones(len(index), bool)
+    if drop is not None:
+        keep[drop] = False
+    shape = (n,) + v.shape[1:]
+    val, unit, mag = np.zeros(shape), np.zeros(shape), np.zeros(shape)
+    np.add.at(unit, index, u)
+    np.add.at(mag, index, np.abs(v))
+    if exact:
+        order = np.argsort(index[keep], kind="stable")
+        vs, idx = v[keep][order].reshape(int(keep.sum()), -1), index[keep][order]
+        ptr = np.searchsorted(idx, np.arange(n + 1))
+        flat = val.reshape(n, -1)
+        for g in range(n):
+            if ptr[g + 1] > ptr[g]:
+                flat[g] = [math.fsum(col) for col in vs[ptr[g]:ptr[g + 1]].T]
+    else:
+        np.add.at(val, index[keep], v[keep])
+    return val, unit + EPS * mag
+
+
+def ba_f64(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0, mut="", exact=False, drop=None):
+    """The float64 restatement of the whole linearisation: (values, units), two dicts over
+    BA_OUTPUTS (values also J [n,2,11], w, rho).  exact: sums by math.fsum.  drop: (mutation g) an
+    observation left out of U."""
+    import math
+    T = ba_terms_f64(cams, pp, pts, cam_idx, pt_idx, uv, loss_s, mut)
+    ci, pi = np.asarray(cam_idx, np.int64), np.asarray(pt_idx, np.int64)
+    nc, npt = len(cams), len(pts)
+    val, unit = {}, {}
+    for k in ("res", "W"):
+        val[k], unit[k] = _stack(T[k], "v"), _stack(T[k], "u")
+    val["U"], unit["U"] = _segment(T["U"], ci, nc, exact, drop)
+    val["gc"], unit["gc"] = _segment(T["gc"], ci, nc, exact)
+    val["V"], unit["V"] = _segment(T["V"], pi, npt, exact)
+    val["gp"], unit["gp"] = _segment(T["gp"], pi, npt, exact)
+    h = T["hrho"]
+    val["cost"] = math.fsum(h.v) if exact else float(np.sum(h.v))
+    unit["cost"] = float(h.u.sum() + EPS * np.abs(h.v).sum())
+    val.update(J=_stack(T["J"], "v"), w=T["w"].v, rho=T["rho"].v)
+    unit.update(J=_stack(T["J"], "u"), rho=T["rho"].u, cost_sum=float(EPS * np.abs(h.v).sum()))
+    return val, unit
+
+
+def ba_units(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0):
+    """The tolerance unit of every entry of res, W, U, V, gc, gp, cost (and J, rho; cost_sum: the
+    summation part eps sum |rho / 2| alone)."""
+    return ba_f64(cams, pp, pts, cam_idx, pt_idx, uv, loss_s)[1]
