@@ -287,9 +287,15 @@ int sfm_ba_jtj(sfm_ctx* ctx, int32_t n_cam, const double* cams, const double* pp
  *     [U + λ D_U   W ; Wᵀ   V + λ D_V] [dc; dp] = -[gc; gp],  D = clamp(diag, 1e-6, 1e32),
  *   by the Schur complement on the points and block-Jacobi preconditioned CG on the cameras
  *   (S is never formed), then back-substitutes dp.  Same CSR inputs as sfm_ba_jtj
- *   (observations point-major).  Stops when |r| <= tol |b| or after max_iter iterations.
+ *   (observations point-major).  Stops when |r| <= tol |b|, after max_iter iterations, or on a
+ *   breakdown: p·q <= 0 (S is not positive definite along the search direction) ends the
+ *   iteration with α = 0, dc and r being those of the last completed step.  A camera whose
+ *   diagonal block S_cc is not positive definite (a pivot of its Cholesky factorisation is not
+ *   > 0) is preconditioned by diag(1 / max(S_ii, 1e-6)) instead of S_cc⁻¹ (the fallback).
  *   out (device): dc [n_cam][8], dp [n_pt][3],
- *   info [5] f64 = {CG iterations, |r|/|b|, gᵀδ, δᵀ JᵀJ δ (undamped), preconditioner fallback}
+ *   info [5] f64 = {CG iterations (the one that broke down included), |r|/|b| of the recurrence
+ *   residual of the last completed iteration (always: a breakdown does not read as converged),
+ *   gᵀδ, δᵀ JᵀJ δ (undamped), bit set: 1 = preconditioner fallback, 2 = CG breakdown}
  *   — the LM predicted decrease is -(gᵀδ + ½ δᵀ JᵀJ δ).
  * sfm_ba_cost:   cost = 0.5 Σ ρ(|r|²) at the given parameters (no Jacobians).
  * sfm_ba_update: cams_out = cams ⊕ dc (R <- exp([δr]x) R, the tangent space of the Jacobians;

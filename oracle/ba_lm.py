@@ -12,6 +12,14 @@ code/3d_reconstruction.py is empty, so the spec is the build's
 * Schur complement on the points: S = U_d - Σ_o W_o V_d⁻¹ W_oᵀ, b = -g_c + Σ_o W_o V_d⁻¹ g_p;
   solved by preconditioned CG with the block-Jacobi preconditioner diag-blocks(S)⁻¹ (Ceres'
   ITERATIVE_SCHUR + SCHUR_JACOBI) — S is never formed, S·x = U_d x - W V_d⁻¹ Wᵀ x;
+  - fallback: a camera whose diagonal block S_cc is not positive definite (a pivot of its 8x8
+    Cholesky factorisation is not > 0; reachable late in a long LM run, λ ~ 1e-16) gets the
+    diagonal preconditioner M_c = diag(1 / max(S_ii, 1e-6)); the other cameras keep S_cc⁻¹;
+  - breakdown: p·q <= 0 (S is not positive definite along the search direction) ends the
+    iteration with α = 0: x and r stay those of the last completed step;
+  - the reported |r|/|b| is always the recurrence residual of the last completed iteration, and
+    both events are reported as a bit set (FLAG_FALLBACK = 1, FLAG_BREAKDOWN = 2), info[4] of
+    sfm_ba_solve;
 * back-substitution δp = V_d⁻¹ (-g_p - Wᵀ δc);
 * update: rotation by a left-multiplied increment R <- exp([δr]x) R (the tangent space the J^TJ
   build differentiates in, oracle/sfm_oracle_ba.c), everything else additive;
@@ -25,6 +33,7 @@ import numpy as np
 import oracle as O
 
 DIAG_MIN, DIAG_MAX = 1e-6, 1e32
+FLAG_FALLBACK, FLAG_BREAKDOWN = 1, 2
 
 
 def damp(A: np.ndarray, lam: float) -> np.ndarray:
@@ -70,14 +79,49 @@ def schur_matvec(Ud, Vinv, W, cam_idx, pt_idx, x):
     return y
 
 
-def schur_pcg(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10):
+def cholesky_pivots(S):
+    """The 8 pivots (the squares of L's diagonal, before the square root) of the Cholesky
+    factorisation of every block of S [n, 8, 8], column by column as the solver takes them; the
+    factorisation goes on with sqrt of a non-positive pivot's magnitude only to fill the rest,
+    which the caller must not use.  A block is positive definite iff all its pivots are > 0."""
+    S = np.asarray(S, np.float64)
+    n, k = S.shape[0], S.shape[-1]
+    L = np.zeros_like(S)
+    piv = np.zeros((n, k))
+    for j in range(k):
+        sv = S[:, j, j] - np.sum(L[:, j, :j] ** 2, axis=1)
+        piv[:, j] = sv
+        d = np.sqrt(np.abs(np.where(sv == 0.0, 1.0, sv)))
+        L[:, j, j] = d
+        for i in range(j + 1, k):
+            L[:, i, j] = (S[:, i, j] - np.sum(L[:, i, :j] * L[:, j, :j], axis=1)) / d
+    return piv
+
+
+def block_preconditioner(S_diag):
+    """(M [n_cam, 8, 8], fallback [n_cam] bool): S_cc⁻¹, or diag(1 / max(S_ii, 1e-6)) for a block
+    that is not positive definite (the first non-positive Cholesky pivot decides)."""
+    piv = cholesky_pivots(S_diag)
+    bad = ~np.all(piv > 0.0, axis=1)
+    M = np.zeros_like(S_diag)
+    M[~bad] = np.linalg.inv(S_diag[~bad])
+    idx = np.arange(S_diag.shape[-1])
+    M[np.nonzero(bad)[0][:, None], idx, idx] = 1.0 / np.maximum(
+        np.diagonal(S_diag[bad], axis1=-2, axis2=-1), DIAG_MIN)
+    return M, bad
+
+
+def schur_pcg(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10, flags=False):
     """The GPU solver's algorithm (same recurrences; summation orders differ).
 
-    Returns (dc [n_cam, 8], dp [n_pt, 3], iters, |r|/|b|)."""
+    Returns (dc [n_cam, 8], dp [n_pt, 3], iters, |r|/|b|), and with flags=True a fifth value: the
+    bit set FLAG_FALLBACK | FLAG_BREAKDOWN (info[4] of sfm_ba_solve).  iters counts the iteration
+    that broke down; |r|/|b| is the recurrence residual of the last completed iteration."""
     cam_idx = np.asarray(cam_idx)
     pt_idx = np.asarray(pt_idx)
     Ud, Vinv, vg, S_diag, b = schur_rhs_and_precond(U, V, W, gc, gp, cam_idx, pt_idx, lam)
-    M = np.linalg.inv(S_diag)
+    M, bad = block_preconditioner(S_diag)
+    flag = FLAG_FALLBACK if bad.any() else 0
     x = np.zeros_like(b)
     r = b.copy()
     bn = np.sqrt(np.sum(b * b))
@@ -88,7 +132,12 @@ def schur_pcg(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10):
     rn = np.sqrt(np.sum(r * r))
     while it < max_iter and rn > tol * bn:
         q = schur_matvec(Ud, Vinv, W, cam_idx, pt_idx, p)
-        alpha = rz / np.sum(p * q)
+        pq = np.sum(p * q)
+        if not pq > 0.0:                                   # breakdown: α = 0, x and r stay
+            flag |= FLAG_BREAKDOWN
+            it += 1
+            break
+        alpha = rz / pq
         x += alpha * p
         r -= alpha * q
         it += 1
@@ -100,7 +149,8 @@ def schur_pcg(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10):
         p = z + (rz_new / rz) * p
         rz = rz_new
     dp = back_substitute(Vinv, vg, W, cam_idx, pt_idx, x)
-    return x, dp, it, (rn / bn if bn > 0 else 0.0)
+    rel = rn / bn if bn > 0 else 0.0
+    return (x, dp, it, rel, flag) if flags else (x, dp, it, rel)
 
 
 def back_substitute(Vinv, vg, W, cam_idx, pt_idx, dc):

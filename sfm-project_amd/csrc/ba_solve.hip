@@ -44,8 +44,9 @@ struct PcgState {
     double bb;      // |b|^2
     double rr;      // |r|^2 after the last step
     int32_t iter;   // iterations done
-    int32_t done;   // converged (or max_iter reached)
+    int32_t done;   // stop: converged, or a CG breakdown (stop below)
     uint32_t cnt;   // blocks of the current vector kernel that finished (last-block publish)
+    int32_t stop;   // CG breakdown (p·q <= 0): set once, ORed into done by publish_next
 };
 
 __device__ __forceinline__ double dclamp(double d) { return fmin(fmax(d, DIAG_MIN), DIAG_MAX); }
@@ -416,7 +417,7 @@ __device__ Scalars pcg_scalars(int k, int n_cam, const double* __restrict__ rzc,
 // barriers per point-pass block).  The same canon_sum association: the same bits.
 __device__ void publish_next(int k, int n_cam, const double* __restrict__ rzc,
                              const double* __restrict__ rrc, double tol, PcgState* __restrict__ st,
-                             unsigned nblk, double* red4x3) {
+                             unsigned nblk, double* red4x3, bool breakdown) {
     __shared__ bool last;
     __threadfence();
     __syncthreads();
@@ -428,7 +429,8 @@ __device__ void publish_next(int k, int n_cam, const double* __restrict__ rzc,
     if (threadIdx.x == 0) {
         st->beta = sc.beta;
         st->rz = sc.rz;
-        st->done = sc.done ? 1 : 0;
+        if (breakdown) st->stop = 1;   // the same decision in every block (canon_sum's bits)
+        st->done = (sc.done || st->stop != 0) ? 1 : 0;
         st->cnt = 0u;
     }
 }
@@ -740,10 +742,12 @@ __global__ __launch_bounds__(CC) void bas_pcg_camera(
 }
 
 // Thread per (camera, component) gi = 8 c + i (a camera's 8 components are 8 consecutive lanes):
-// α = rz_k / Σ p·q; x += α p; r -= α q; z = M r; per-camera r·z and r·r into slot (k+1)&1 (rr = 0
-// on a breakdown).  A breakdown (p·q <= 0) stops the iteration.  The component's x, p, r, q and
-// its row of M are loaded before canon_sum's barriers (they do not depend on α), so their latency
-// overlaps the reduction's (round 6: the kernel is a chain of dependent global round trips).
+// α = rz_k / Σ p·q; x += α p; r -= α q; z = M r; per-camera r·z and r·r into slot (k+1)&1.  A
+// breakdown (p·q <= 0: S is not positive definite along p) takes α = 0, so x and r stay and r·r
+// is still the true one, and stops the iteration through PcgState::stop.  The component's x, p,
+// r, q and its row of M are loaded before canon_sum's barriers (they do not depend on α), so
+// their latency overlaps the reduction's (round 6: the kernel is a chain of dependent global
+// round trips).
 __global__ __launch_bounds__(256) void bas_pcg_vec(
     int k, int n_cam, const double* __restrict__ Mc, double* __restrict__ x,
     double* __restrict__ r, double* __restrict__ z, const double* __restrict__ pv,
@@ -795,11 +799,11 @@ __global__ __launch_bounds__(256) void bas_pcg_vec(
         z[kk] = zi;
         if (i == 0) {
             rzc[(size_t)s1 * n_cam + c] = rz;
-            rrc[(size_t)s1 * n_cam + c] = breakdown ? 0.0 : rr;
+            rrc[(size_t)s1 * n_cam + c] = rr;   // the true |r|^2, a breakdown included (α = 0)
         }
     }
     if (gi == 0) st->iter = k + 1;
-    publish_next(k, n_cam, rzc, rrc, tol, st, gridDim.x, red4);
+    publish_next(k, n_cam, rzc, rrc, tol, st, gridDim.x, red4, breakdown);
 }
 
 // ---- explicit reduced camera system (sfm_ba_set_schur) -------------------------------------------
@@ -940,6 +944,7 @@ __device__ void pcg_init_body(int n_cam, const double* __restrict__ rzc,
         st->iter = 0;
         st->done = sc.done ? 1 : 0;
         st->cnt = 0u;
+        st->stop = 0;
     }
 }
 
@@ -1168,11 +1173,11 @@ __global__ __launch_bounds__(FV) void bas_pcg_finish_vec(
         z[kk] = zi;
         if (i == 0) {
             rzc[(size_t)s1 * n_cam + c] = rz;
-            rrc[(size_t)s1 * n_cam + c] = breakdown ? 0.0 : rr;
+            rrc[(size_t)s1 * n_cam + c] = rr;   // the true |r|^2, a breakdown included (α = 0)
         }
     }
     if (blockIdx.x == 0 && tid == 0) st->iter += 1;  // k-free: a captured window replays at any k
-    publish_next(k, n_cam, rzc, rrc, tol, st, gridDim.x, red4);
+    publish_next(k, n_cam, rzc, rrc, tol, st, gridDim.x, red4, breakdown);
 }
 
 // One block: |b|^2 (canonical sum of the setup's per-camera shares) and the iteration count.
@@ -1422,7 +1427,8 @@ __global__ __launch_bounds__(1024) void bas_mpart_total(int n_pblk, const double
 }
 
 // One block: camera terms (g_c·δc, δcᵀ U δc) + the point-block partials -> info.
-//   info = {iterations, |r|/|b|, gᵀδ, δᵀ JᵀJ δ, preconditioner fallback (0/1)}
+//   info = {iterations, |r|/|b| of the last iteration's recurrence residual, gᵀδ, δᵀ JᵀJ δ,
+//           bit set: 1 = preconditioner fallback, 2 = CG breakdown}
 // Chunk mode (nck > 0 or ntot > 0): the back-substitution's model partials are the chunk tree of
 // bas_mchunk's non-export form — formed here by wave 0 (the same code, the same bits) and taken by
 // thread 0 where it took the separate kernel's total, one launch fewer per solve.
@@ -1467,7 +1473,7 @@ __global__ __launch_bounds__(1024) void bas_model(int n_cam, int n_pblk, const d
         info[1] = st->bb > 0.0 ? sqrt(rr / st->bb) : 0.0;
         info[2] = ga;
         info[3] = qb;
-        info[4] = (double)*bad;
+        info[4] = (double)(*bad | (st->stop != 0 ? 2 : 0));
     }
 }
 

@@ -634,7 +634,8 @@ class Context:
     def ba_solve(self, lin, cam_idx, pt_idx, pt_ptr, cam_ptr, cam_obs, lam, max_iter=100,
                  tol=1e-10, out=None, poll=8, poll_first=0):
         """Damped Schur-complement PCG step from the ba_jtj blocks `lin`; returns
-        (dc [n_cam,8], dp [n_pt,3], info [5] f64 device tensor).  poll: convergence poll period
+        (dc [n_cam,8], dp [n_pt,3], info [5] f64 device tensor: iterations, |r|/|b|, the two model
+        terms, bit set 1 = preconditioner fallback | 2 = CG breakdown).  poll: convergence poll period
         in CG iterations (one host sync each; <= 0 = none, fully asynchronous / graph-capturable);
         poll_first > 0: the first poll at that iteration; see include/sfmcore.h."""
         torch = self.torch

@@ -16,6 +16,11 @@ float64 inputs, so the only error a comparison charges to the code under test is
   ba_residuals(...)                           residuals, rho and the cost alone (large problems)
   ba_f64(...), ba_units(...)                  float64 restatement of the linearisation carrying a
                                               first-order error unit for every entry
+  solve_blocks(U, V, W, gc, gp, ci, pi, lam)  the BA step solve (csrc/ba_solve.hip) on the float64
+                                              blocks: a SolveRef with V_d^-1, its condition, b, the
+                                              implicit S x, solve_residual, solve_backsub,
+                                              solve_direct, model_terms and the units of each
+  solve_f64(...)                              float64 restatement of the solve with a mut switch
 """
 from __future__ import annotations
 
@@ -533,3 +538,406 @@ def ba_units(cams, pp, pts, cam_idx, pt_idx, uv, loss_s=0.0):
     """The tolerance unit of every entry of res, W, U, V, gc, gp, cost (and J, rho; cost_sum: the
     summation part eps sum |rho / 2| alone)."""
     return ba_f64(cams, pp, pts, cam_idx, pt_idx, uv, loss_s)[1]
+
+
+# ---- bundle-adjustment step solve -----------------------------------------------------------------
+# Spec (include/sfmcore.h sfm_ba_solve, the header of csrc/ba_solve.hip): from the float64 blocks
+# U, V, W, g_c, g_p (exact inputs here) and λ,
+#   A_d = A + λ clamp(diag A, 1e-6, 1e32),  S = U_d - Σ_o W_o V_d⁻¹ W_oᵀ,  b = -g_c + Σ_o W_o V_d⁻¹ g_p,
+#   S δc = b,  δp = V_d⁻¹ (-g_p - Σ_o W_oᵀ δc)  (δp = 0 for a point without observations),
+#   model terms gᵀδ and δᵀ JᵀJ δ with the undamped blocks.
+# Fixed parameters enter through the blocks (sfm_ba_fix_params / ba_lm.fix_params change them
+# exactly), so the reference takes the blocks after that.
+
+SOLVE_DIAG_MIN, SOLVE_DIAG_MAX = 1e-6, 1e32      # the float64 constants of the spec
+SOLVE_CLASSES = (("r", slice(0, 3)), ("t", slice(3, 6)), ("f", slice(6, 7)), ("k1", slice(7, 8)))
+
+
+def _mpl(a):
+    """Nested lists of mpf from a float64 array."""
+    a = np.asarray(a, np.float64)
+    if a.ndim == 1:
+        return [mp.mpf(float(x)) for x in a]
+    return [_mpl(x) for x in a]
+
+
+class SolveRef:
+    """The 50-digit reference of one step solve (solve_blocks).  Attributes (float64 arrays unless
+    said): Vinv [n_pt,3,3] (V_d⁻¹ rounded; zero for unobserved points), kappa [n_pt] = κ₂(V_d),
+    ninv [n_pt] = ‖V_d⁻¹‖₂ (both 1 / 0 for unobserved points), b [n_cam,8]; 50-digit copies
+    Vinv_hp, b_hp, Ud_hp.  Methods: S_mul, solve_residual, solve_backsub, solve_direct,
+    model_terms and the units unit_backsub, unit_residual, unit_model."""
+
+    @_hp
+    def __init__(self, U, V, W, gc, gp, cam_idx, pt_idx, lam):
+        f = lambda a, shape: np.ascontiguousarray(a, np.float64).reshape(shape)
+        self.U, self.V, self.W = f(U, (-1, 8, 8)), f(V, (-1, 3, 3)), f(W, (-1, 8, 3))
+        self.gc, self.gp = f(gc, (-1, 8)), f(gp, (-1, 3))
+        self.ci = [int(c) for c in cam_idx]
+        self.pi = [int(p) for p in pt_idx]
+        self.nc, self.npt, self.no = len(self.U), len(self.V), len(self.ci)
+        self.lam = float(lam)
+        self.seen = np.bincount(np.asarray(self.pi, np.int64), minlength=self.npt) > 0
+        lm = mp.mpf(self.lam)
+        lo, hi = mp.mpf(SOLVE_DIAG_MIN), mp.mpf(SOLVE_DIAG_MAX)
+        damp = lambda d: d + lm * min(max(d, lo), hi)
+        self.U_hp, self.V_hp, self.W_hp = _mpl(self.U), _mpl(self.V), _mpl(self.W)
+        self.gc_hp, self.gp_hp = _mpl(self.gc), _mpl(self.gp)
+        self.Ud_hp = [[[damp(B[i][j]) if i == j else B[i][j] for j in range(8)] for i in range(8)]
+                      for B in self.U_hp]
+        zero = mp.mpf(0)
+        self.Vinv_hp, self.kappa, self.ninv = [], np.ones(self.npt), np.zeros(self.npt)
+        for p in range(self.npt):
+            if not self.seen[p]:
+                self.Vinv_hp.append([[zero] * 3 for _ in range(3)])
+                continue
+            B = self.V_hp[p]
+            Vd = [[damp(B[i][j]) if i == j else B[i][j] for j in range(3)] for i in range(3)]
+            self.Vinv_hp.append(_inv3(Vd))
+            ev = sorted(abs(x) for x in mp.eigsy(mp.matrix(Vd), eigvals_only=True))
+            self.kappa[p], self.ninv[p] = float(ev[2] / ev[0]), float(1 / ev[0])
+        self.Vinv = np.array([[[float(x) for x in r] for r in B] for B in self.Vinv_hp]
+                             ).reshape(self.npt, 3, 3)
+        vg = [_mv(self.Vinv_hp[p], self.gp_hp[p]) for p in range(self.npt)]
+        b = [[-x for x in g] for g in self.gc_hp]
+        for o in range(self.no):
+            Wo, v, bc = self.W_hp[o], vg[self.pi[o]], b[self.ci[o]]
+            for i in range(8):
+                bc[i] += Wo[i][0] * v[0] + Wo[i][1] * v[1] + Wo[i][2] * v[2]
+        self.b_hp = b
+        self.b = np.array([[float(x) for x in r] for r in b]).reshape(self.nc, 8)
+        self.bnorm_hp = mp.sqrt(sum(x * x for r in b for x in r))
+        self._direct = None
+
+    # -- products ---------------------------------------------------------------------------
+    def _wt(self, x):
+        """Σ_o W_oᵀ x_c per point (x: [n_cam][8] of mpf)."""
+        t = [[mp.mpf(0)] * 3 for _ in range(self.npt)]
+        for o in range(self.no):
+            Wo, xc, tp = self.W_hp[o], x[self.ci[o]], t[self.pi[o]]
+            for j in range(3):
+                s = tp[j]
+                for i in range(8):
+                    s += Wo[i][j] * xc[i]
+                tp[j] = s
+        return t
+
+    @_hp
+    def S_mul(self, x):
+        """The implicit S·x = U_d x - Σ_o W_o V_d⁻¹ Σ_o' W_o'ᵀ x in 50 digits; x [n_cam, 8]
+        float64 or nested mpf; returns nested mpf."""
+        x = _mpl(x) if isinstance(x, np.ndarray) else x
+        t = [_mv(self.Vinv_hp[p], tp) for p, tp in enumerate(self._wt(x))]
+        y = [_mv(self.Ud_hp[c], x[c]) for c in range(self.nc)]
+        for o in range(self.no):
+            Wo, tp, yc = self.W_hp[o], t[self.pi[o]], y[self.ci[o]]
+            for i in range(8):
+                yc[i] -= Wo[i][0] * tp[0] + Wo[i][1] * tp[1] + Wo[i][2] * tp[2]
+        return y
+
+    @_hp
+    def solve_residual(self, dc):
+        """‖b - S·dc‖₂ / ‖b‖₂ for a float64 dc (0 when b = 0), as a float."""
+        if self.bnorm_hp == 0:
+            return 0.0
+        y = self.S_mul(np.asarray(dc, np.float64).reshape(self.nc, 8))
+        rr = sum((bi - yi) ** 2 for bc, yc in zip(self.b_hp, y) for bi, yi in zip(bc, yc))
+        return float(mp.sqrt(rr) / self.bnorm_hp)
+
+    @_hp
+    def solve_backsub(self, dc, hp=False):
+        """δp(dc) = V_d⁻¹ (-g_p - Σ_o W_oᵀ dc_c) per point for a float64 (or nested mpf) dc:
+        float64 [n_pt, 3], or nested mpf with hp=True."""
+        x = _mpl(np.asarray(dc, np.float64).reshape(self.nc, 8)) if not isinstance(dc, list) else dc
+        t = self._wt(x)
+        out = [_mv(self.Vinv_hp[p], [-g - s for g, s in zip(self.gp_hp[p], t[p])])
+               for p in range(self.npt)]
+        return out if hp else np.array([[float(v) for v in r] for r in out]).reshape(self.npt, 3)
+
+    @_hp
+    def backsub_error(self, dc, dp):
+        """(‖dp - δp(dc)‖₂ per point with the difference taken in 50 digits, ‖δp(dc)‖₂ per point);
+        a NaN or an infinity in dp gives inf."""
+        ref = self.solve_backsub(dc, hp=True)
+        dp = np.asarray(dp, np.float64).reshape(self.npt, 3)
+        err, nrm = np.zeros(self.npt), np.zeros(self.npt)
+        for p in range(self.npt):
+            nrm[p] = float(mp.sqrt(sum(v * v for v in ref[p])))
+            if not np.all(np.isfinite(dp[p])):
+                err[p] = np.inf
+                continue
+            err[p] = float(mp.sqrt(sum((mp.mpf(float(a)) - v) ** 2 for a, v in zip(dp[p], ref[p]))))
+        return err, nrm
+
+    @_hp
+    def solve_direct(self):
+        """(δc* [n_cam, 8], δp* [n_pt, 3]) float64: dense S in 50 digits, mp.lu_solve, then the
+        back-substitution of the 50-digit δc*.  Small problems only; cached."""
+        if self._direct is None:
+            assert self.nc <= 12, "solve_direct: small problems only"
+            n = 8 * self.nc
+            S = mp.zeros(n, n)
+            for c in range(self.nc):
+                for i in range(8):
+                    for j in range(8):
+                        S[8 * c + i, 8 * c + j] = self.Ud_hp[c][i][j]
+            obs_of = [[] for _ in range(self.npt)]
+            for o, p in enumerate(self.pi):
+                obs_of[p].append(o)
+            for p, obs in enumerate(obs_of):
+                Vi = self.Vinv_hp[p]
+                Y = {o: [[sum(self.W_hp[o][i][k] * Vi[k][j] for k in range(3)) for j in range(3)]
+                         for i in range(8)] for o in obs}
+                for a in obs:
+                    ra = 8 * self.ci[a]
+                    for b in obs:
+                        rb, Wb = 8 * self.ci[b], self.W_hp[b]
+                        for i in range(8):
+                            Yi = Y[a][i]
+                            for j in range(8):
+                                S[ra + i, rb + j] -= Yi[0] * Wb[j][0] + Yi[1] * Wb[j][1] + Yi[2] * Wb[j][2]
+            x = mp.lu_solve(S, mp.matrix([v for r in self.b_hp for v in r]))
+            dc = [[x[8 * c + i] for i in range(8)] for c in range(self.nc)]
+            dp = self.solve_backsub(dc, hp=True)
+            self._direct = (np.array([[float(v) for v in r] for r in dc]).reshape(self.nc, 8),
+                            np.array([[float(v) for v in r] for r in dp]).reshape(self.npt, 3))
+        return self._direct
+
+    def direct_error(self, dc, dp):
+        """max |δ - δ*| / max |δ*| per parameter class (r, t, f, k1, X); a class whose δ* is all
+        zero must be matched exactly (else inf); a NaN or an infinity gives inf."""
+        sc, sp = self.solve_direct()
+        dc, dp = np.asarray(dc, np.float64).reshape(sc.shape), np.asarray(dp, np.float64).reshape(sp.shape)
+        out = {}
+        for name, a, b in [(n, dc[:, s], sc[:, s]) for n, s in SOLVE_CLASSES] + [("X", dp, sp)]:
+            if a.size == 0:
+                continue
+            d, m = np.abs(a - b).max(), np.abs(b).max()
+            ok = np.all(np.isfinite(a))
+            out[name] = float(d / m) if ok and m > 0 else (0.0 if ok and d == 0 else np.inf)
+        return out
+
+    @_hp
+    def model_terms(self, dc, dp):
+        """(gᵀδ, δᵀ JᵀJ δ) of a float64 δ with the undamped blocks, summed in 50 digits."""
+        x = _mpl(np.asarray(dc, np.float64).reshape(self.nc, 8))
+        y = _mpl(np.asarray(dp, np.float64).reshape(self.npt, 3)) if self.npt else []
+        gd = sum(g * v for gr, xr in zip(self.gc_hp, x) for g, v in zip(gr, xr))
+        gd += sum(g * v for gr, yr in zip(self.gp_hp, y) for g, v in zip(gr, yr))
+        q = sum(xc[i] * sum(B[i][j] * xc[j] for j in range(8)) for B, xc in zip(self.U_hp, x)
+                for i in range(8))
+        q += sum(yp[i] * sum(B[i][j] * yp[j] for j in range(3)) for B, yp in zip(self.V_hp, y)
+                 for i in range(3))
+        for o in range(self.no):
+            Wo, xc, yp = self.W_hp[o], x[self.ci[o]], y[self.pi[o]]
+            q += 2 * sum(xc[i] * (Wo[i][0] * yp[0] + Wo[i][1] * yp[1] + Wo[i][2] * yp[2])
+                         for i in range(8))
+        return float(gd), float(q)
+
+    @_hp
+    def first_iterate(self):
+        """The CG's first iterate x_1 = α M b, α = b·z / z·S z, z = M b, in 50 digits, with M as
+        the spec states it: per camera the inverse of S_cc = U_d - Σ_o W_o V_d⁻¹ W_oᵀ over the
+        camera's observations, or diag(1 / max(S_ii, 1e-6)) where a pivot of S_cc's Cholesky
+        factorisation is not > 0.  Returns (x1 [n_cam, 8] float64, fallback [n_cam] bool,
+        unit [n_cam]): unit_c = eps (κ₂(S_cc) + c_α) ‖x1_c‖₂, the forward error of a
+        backward-stable solve with S_cc (κ = 1 for the diagonal form) plus the rounding of α,
+        c_α = Σ|b_i z_i| / |b·z| + Σ|z_i (S z)_i| / |z·S z|."""
+        S = [[row[:] for row in B] for B in self.Ud_hp]
+        for o in range(self.no):
+            Wo, Vi, Sc = self.W_hp[o], self.Vinv_hp[self.pi[o]], S[self.ci[o]]
+            Y = [_mv([[Vi[k][j] for k in range(3)] for j in range(3)], Wo[i]) for i in range(8)]
+            for i in range(8):
+                for j in range(8):
+                    Sc[i][j] -= Y[i][0] * Wo[j][0] + Y[i][1] * Wo[j][1] + Y[i][2] * Wo[j][2]
+        lo = mp.mpf(SOLVE_DIAG_MIN)
+        z, bad, kap = [], np.zeros(self.nc, bool), np.ones(self.nc)
+        for c in range(self.nc):
+            A = mp.matrix(S[c])
+            L = mp.zeros(8, 8)
+            for j in range(8):
+                sv = A[j, j] - sum(L[j, k] ** 2 for k in range(j))
+                if not sv > 0:
+                    bad[c] = True
+                    break
+                L[j, j] = mp.sqrt(sv)
+                for i in range(j + 1, 8):
+                    L[i, j] = (A[i, j] - sum(L[i, k] * L[j, k] for k in range(j))) / L[j, j]
+            if bad[c]:
+                z.append([self.b_hp[c][i] / max(S[c][i][i], lo) for i in range(8)])
+            else:
+                z.append(list(mp.lu_solve(A, mp.matrix(self.b_hp[c]))))
+                ev = sorted(abs(x) for x in mp.eigsy(A, eigvals_only=True))
+                kap[c] = float(ev[-1] / ev[0])
+        q = self.S_mul(z)
+        bz = [bi * zi for bc, zc in zip(self.b_hp, z) for bi, zi in zip(bc, zc)]
+        zq = [zi * qi for zc, qc in zip(z, q) for zi, qi in zip(zc, qc)]
+        alpha = sum(bz) / sum(zq)
+        c_alpha = float(sum(abs(t) for t in bz) / abs(sum(bz)) + sum(abs(t) for t in zq) / abs(sum(zq)))
+        x1 = np.array([[float(alpha * v) for v in zc] for zc in z]).reshape(self.nc, 8)
+        return x1, bad, EPS * (kap + c_alpha) * np.linalg.norm(x1, axis=1)
+
+    # -- units (float64: a unit needs no more) -------------------------------------------------
+    def unit_backsub(self, dc, ref_norm):
+        """u_p = eps (κ₂(V_d) ‖δp_ref‖₂ + ‖V_d⁻¹‖₂ (‖g_p‖₁ + Σ_o ‖|W_o|ᵀ|dc_c|‖₁)) per point: the
+        forward error of a backward-stable 3x3 solve plus the rounding of its right-hand side."""
+        a = np.abs(np.asarray(dc, np.float64).reshape(self.nc, 8))
+        rhs = np.abs(self.gp).sum(1)
+        if self.no:
+            np.add.at(rhs, np.asarray(self.pi), np.einsum("oij,oi->oj", np.abs(self.W),
+                                                          a[np.asarray(self.ci)]).sum(1))
+        return EPS * (self.kappa * np.asarray(ref_norm) + self.ninv * rhs)
+
+    def unit_residual(self, dc):
+        """u_r = eps ‖ |U_d||dc| + Σ |W||V_d⁻¹||W|ᵀ|dc| + |b| ‖₂ / ‖b‖₂: one rounding of one
+        evaluation of b - S·dc (0 when b = 0)."""
+        bn = float(self.bnorm_hp)
+        if bn == 0.0:
+            return 0.0
+        a = np.abs(np.asarray(dc, np.float64).reshape(self.nc, 8))
+        Ud = np.abs(np.array([[[float(v) for v in r] for r in B] for B in self.Ud_hp]))
+        v = np.einsum("cij,cj->ci", Ud.reshape(self.nc, 8, 8), a) + np.abs(self.b)
+        if self.no:
+            ci, pi, Wa = np.asarray(self.ci), np.asarray(self.pi), np.abs(self.W)
+            t = np.zeros((self.npt, 3))
+            np.add.at(t, pi, np.einsum("oij,oi->oj", Wa, a[ci]))
+            t = np.einsum("pij,pj->pi", np.abs(self.Vinv), t)
+            np.add.at(v, ci, np.einsum("oij,oj->oi", Wa, t[pi]))
+        return EPS * float(np.sqrt((v * v).sum())) / bn
+
+    def unit_model(self, dc, dp):
+        """(eps Σ|term| of gᵀδ, eps Σ|term| of δᵀ JᵀJ δ)."""
+        a = np.abs(np.asarray(dc, np.float64).reshape(self.nc, 8))
+        d = np.abs(np.asarray(dp, np.float64).reshape(self.npt, 3))
+        gd = (np.abs(self.gc) * a).sum() + (np.abs(self.gp) * d).sum()
+        q = np.einsum("ci,cij,cj->", a, np.abs(self.U), a) + np.einsum("pi,pij,pj->", d, np.abs(self.V), d)
+        if self.no:
+            q += 2.0 * np.einsum("oi,oij,oj->", a[np.asarray(self.ci)], np.abs(self.W),
+                                 d[np.asarray(self.pi)])
+        return EPS * float(gd), EPS * float(q)
+
+
+def _mv(A, x):
+    return [sum(a * v for a, v in zip(row, x)) for row in A]
+
+
+def _inv3(A):
+    """Inverse of a 3x3 nested-mpf matrix (adjugate / determinant: exact enough at 50 digits)."""
+    (a, b, c), (d, e, f), (g, h, i) = A
+    C = [[e * i - f * h, c * h - b * i, b * f - c * e],
+         [f * g - d * i, a * i - c * g, c * d - a * f],
+         [d * h - e * g, b * g - a * h, a * e - b * d]]
+    det = a * C[0][0] + b * C[1][0] + c * C[2][0]
+    return [[x / det for x in row] for row in C]
+
+
+def solve_blocks(U, V, W, gc, gp, cam_idx, pt_idx, lam):
+    """The 50-digit reference of sfm_ba_solve on the float64 blocks (after any fix_params)."""
+    return SolveRef(U, V, W, gc, gp, cam_idx, pt_idx, lam)
+
+
+# Float64 restatement of the whole solve (written from the spec, numpy), with the mutations of the
+# mutation check in tests/test_ba_solve_hp_cpu.py; mut is never set otherwise.
+SOLVE_MUTATIONS = dict(
+    a="damping without the clamp", b="W_o read as its transpose's layout in the CG point sum",
+    c="one observation of the 257-track dropped from the back-substitution's sum",
+    d="a 65-observation point's dp left at its set-up value -V_d^-1 g_p",
+    e="S p with the undamped U", f="+g_p for -g_p in the back-substitution",
+    g="the last camera's z = M r skipped", h="info[1] forced to 0 on a breakdown")
+
+
+def solve_f64(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10, mut=""):
+    """(dc, dp, info [5]) as sfm_ba_solve returns them: fallback, breakdown and info as the spec
+    states them.  mut: a key of SOLVE_MUTATIONS."""
+    U, V, W = (np.asarray(a, np.float64) for a in (U, V, W))
+    gc, gp = np.asarray(gc, np.float64), np.asarray(gp, np.float64)
+    ci, pi = np.asarray(cam_idx, np.int64), np.asarray(pt_idx, np.int64)
+    nc, npt = len(U), len(V)
+    cnt = np.bincount(pi, minlength=npt)
+
+    def damp(A):
+        d = np.diagonal(A, axis1=-2, axis2=-1)
+        d = d if mut == "a" else np.clip(d, SOLVE_DIAG_MIN, SOLVE_DIAG_MAX)
+        out = A.copy()
+        k = np.arange(A.shape[-1])
+        out[..., k, k] += lam * d
+        return out
+
+    Vinv = np.zeros_like(V)
+    if (cnt > 0).any():
+        Vinv[cnt > 0] = np.linalg.inv(damp(V)[cnt > 0])
+    vg = np.einsum("pij,pj->pi", Vinv, gp)
+    Ud = damp(U)
+    Wt = W.reshape(-1, 3, 8).transpose(0, 2, 1) if mut == "b" else W
+
+    def wt(x, Wm=W, skip=None):
+        t = np.zeros((npt, 3))
+        term = np.einsum("oij,oi->oj", Wm, x[ci])
+        if skip is not None:
+            term[skip] = 0.0
+        np.add.at(t, pi, term)
+        return t
+
+    def smul(x):
+        t = np.einsum("pij,pj->pi", Vinv, wt(x, Wt))
+        y = np.einsum("cij,cj->ci", U if mut == "e" else Ud, x)
+        np.subtract.at(y, ci, np.einsum("oij,oj->oi", W, t[pi]))
+        return y
+
+    Scc = Ud.copy()
+    np.subtract.at(Scc, ci, np.einsum("oik,ojk->oij", np.einsum("oij,ojk->oik", W, Vinv[pi]), W))
+    b = -gc.copy()
+    np.add.at(b, ci, np.einsum("oij,oj->oi", W, vg[pi]))
+    M, flag = np.zeros_like(Scc), 0
+    for c in range(nc):
+        try:
+            np.linalg.cholesky(Scc[c])
+            M[c] = np.linalg.inv(Scc[c])
+        except np.linalg.LinAlgError:
+            M[c] = np.diag(1.0 / np.maximum(np.diag(Scc[c]), SOLVE_DIAG_MIN))
+            flag |= 1
+
+    def precond(r, z_old):
+        z = np.einsum("cij,cj->ci", M, r)
+        if mut == "g" and z_old is not None:
+            z[-1] = z_old[-1]
+        return z
+
+    x, r = np.zeros_like(b), b.copy()
+    bb = float((b * b).sum())
+    z = precond(r, None)
+    p, rz, rr, it = z.copy(), float((r * z).sum()), bb, 0
+    broke = False
+    while it < max_iter and bb > 0.0 and rr > tol * tol * bb:
+        q = smul(p)
+        pq = float((p * q).sum())
+        it += 1
+        if not pq > 0.0:
+            flag |= 2
+            broke = True
+            break
+        al = float(np.float64(rz) / np.float64(pq))
+        x += al * p
+        r -= al * q
+        rr = float((r * r).sum())
+        z = precond(r, z)
+        rz_new = float((r * z).sum())
+        with np.errstate(all="ignore"):           # a mutation may end in 0 / 0: as the kernel, NaN
+            p = z + (np.float64(rz_new) / np.float64(rz)) * p
+        rz = rz_new
+    keep = None
+    if mut == "c":
+        long = np.nonzero(cnt == 257)[0]
+        keep = int(np.nonzero(pi == long[0])[0][100]) if len(long) else None
+    sign = 1.0 if mut == "f" else -1.0
+    dp = sign * vg - np.einsum("pij,pj->pi", Vinv, wt(x, W, keep))
+    if mut == "d":
+        sel = np.nonzero(cnt == 65)[0]
+        dp[sel[:1]] = -vg[sel[:1]]
+    gd = float((gc * x).sum() + (gp * dp).sum())
+    qq = float(np.einsum("ci,cij,cj->", x, U, x) + np.einsum("pi,pij,pj->", dp, V, dp)
+               + 2.0 * np.einsum("oi,oij,oj->", x[ci], W, dp[pi]))
+    rel = np.sqrt(rr / bb) if bb > 0.0 else 0.0
+    if mut == "h" and broke:
+        rel = 0.0
+    return x, dp, np.array([it, rel, gd, qq, flag], np.float64)
