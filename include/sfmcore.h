@@ -456,6 +456,39 @@ int sfm_triangulate(sfm_ctx* ctx, int32_t n_cam, const double* cams, const doubl
                     int32_t n_pt, const int32_t* pt_ptr, const int32_t* cam_idx, const double* uv,
                     double* out_pts, double* out_stats);
 
+/* Robust triangulation (papers/schoenberger2016sfm.pdf §4.2): RANSAC over the view
+ * pairs of every track.  A pair's midpoint (ray angle above the gate, both ray parameters
+ * positive) is scored by the observations that conform to it (positive depth, reprojection error
+ * under the full camera model below thr); the consensus set of the winner is refitted by
+ * sfm_triangulate's DLT.  fp64 in a fixed operation order: the spec is the header of
+ * csrc/triangulate_robust.hip, tests/tri_ref.c restates it and the results equal it bit for bit.
+ * Inputs as sfm_triangulate, plus pt_id [n_pt] i32: hypothesis h of a track depends only on
+ * (seed, pt_id, h) and the track's own observations, never on the rest of the batch.
+ *   out (device): pts [n_pt][3] f64; stats [n_pt][4] f64 = sfm_triangulate's, over the consensus
+ *   set {mean reprojection error, largest ray angle (deg), smallest depth, status}; mask [n_obs]
+ *   u8, 1 = the observation conforms to the returned point; info [n_pt][2] i32 = {consensus
+ *   size, winning hypothesis}.  Status 0 ok, 1 fewer than 2 observations, 4 no admissible
+ *   hypothesis; unless it is 0 the track's point, mask, stats[0..2] and info[0] are zero and
+ *   info[1] is -1. */
+typedef struct sfm_triangulate_robust_params {
+    int32_t struct_size; /* sizeof(sfm_triangulate_robust_params) of the caller */
+    int32_t max_hyp;     /* 1 .. 1024 view pairs per track (all pairs if there are no more) */
+    double thr;          /* conformity threshold, pixels, > 0 */
+    double max_cos2;     /* cos^2 of the smallest admissible ray angle, in (0, 1] */
+    uint64_t seed;
+} sfm_triangulate_robust_params;
+int sfm_triangulate_robust(sfm_ctx* ctx, int32_t n_cam, const double* cams, const double* pp,
+                           int32_t n_pt, const int32_t* pt_ptr, const int32_t* cam_idx,
+                           const double* uv, const int32_t* pt_id,
+                           const sfm_triangulate_robust_params* prm, double* out_pts,
+                           double* out_stats, uint8_t* out_mask, int32_t* out_info);
+
+/* The per-camera table both triangulation calls start from (device, out_tab [n_cam][20] f64 =
+ * R (9, row-major), t (3), centre -R^T t (3), f, k1, pp (2), 0): what the fixed-order spec of
+ * sfm_triangulate_robust takes as its input. */
+int sfm_triangulate_cam_table(sfm_ctx* ctx, int32_t n_cam, const double* cams, const double* pp,
+                              double* out_tab);
+
 /* ---- next-view registration ---------------------------------------------------------------
  * registers a batch of images against triangulated points (P3P RANSAC +
  * Gauss-Newton refinement; spec in oracle/sfm_oracle_reg.c / csrc/register.hip).  Per image i:

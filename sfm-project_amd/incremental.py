@@ -77,6 +77,8 @@ class Reconstruction:
         self.gauge = None          # (reference camera, scale camera) of the initial pair
         self._tracks_d = None      # device (ptr, img, kp) of the tracks; host copies on first use
         self._tracks = None
+        self.obs_ok_d = None       # reconstruct(triangulation="ransac"): device [n_obs] bool, the
+        #                            observation is still believed; .obs_ok is the host copy
 
     @property
     def tracks(self):
@@ -103,6 +105,12 @@ class Reconstruction:
         """[n_tr] bool host copy: the track has a triangulated point (read-only and cached, see
         points)."""
         return self._host("has", self.has_d)
+
+    @property
+    def obs_ok(self):
+        """[n_obs] bool host copy of obs_ok_d (None under the default triangulation; read-only
+        and cached, see points)."""
+        return self._host("obs_ok", self.obs_ok_d)
 
     def _host(self, name, t):
         if t is None:
@@ -224,7 +232,7 @@ def point_mean(err, first):
 def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max_err=4.0,
                 ba_iter=20, loss_s=2.0, device=0, log=None, group=None, shard_ba=False,
                 ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6, init_pair="inliers",
-                init_candidates=64):
+                init_candidates=64, triangulation="dlt"):
     """desc [n_img,K,D] u8, kps [n_img,K,2] pixels, n_kp [n_img], intr [n_img,4] = (f, k1, cx, cy).
     Returns a Reconstruction (cams [n_img,8], registered mask, points per track, track arrays).
     With torch.distributed initialised (one process per GPU, `group` or the default group) the
@@ -247,11 +255,22 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     "pose": the `init_candidates` pairs with the most inliers go through the GPU pose batch
     (sfm_two_view_pose_batch) and are tried by descending n_wide, the number of inliers whose
     triangulation angle exceeds 2 degrees, each under the batch's winning pose only — on a dense
-    sequence the most-matched pairs are the narrowest ones (_initial_pair_by_pose)."""
+    sequence the most-matched pairs are the narrowest ones (_initial_pair_by_pose).
+    triangulation: "dlt" (the default): every observation of a track enters its point, and the
+    track stands or falls as a whole.  "ransac": sfm_triangulate_robust (RANSAC over the track's
+    view pairs, keyed by the track id, threshold max_err) finds the observations that agree;
+    rec.obs_ok_d / rec.obs_ok flag the observations still believed: one excluded by the
+    triangulation's mask, or left above max_err by a bundle adjustment, stays out of the later
+    adjustments, and a point with fewer than two believed observations in registered images is
+    dropped."""
     import time
     import torch
     if init_pair not in ("inliers", "pose"):
         raise ValueError(f"reconstruct: init_pair must be 'inliers' or 'pose', got {init_pair!r}")
+    if triangulation not in ("dlt", "ransac"):
+        raise ValueError(f"reconstruct: triangulation must be 'dlt' or 'ransac', "
+                         f"got {triangulation!r}")
+    robust = triangulation == "ransac"
     dev = torch.device("cuda", device)
     ctx = sfmcore.context(device)
     say = log or (lambda *a: None)
@@ -292,6 +311,8 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     rec.pts_d = torch.zeros((n_tr, 3), dtype=torch.float64, device=dev)
     rec.has_d = torch.zeros(n_tr, dtype=torch.bool, device=dev)
     rec.cams[:, 6:8] = intr[:, :2]
+    if robust:
+        rec.obs_ok_d = torch.ones(obs_d[0].shape[0], dtype=torch.bool, device=dev)
 
     # ---- initial pair: most verified inliers; relative pose from that pair's RANSAC-verified
     # matches (tracks may still carry a wrong observation), then its tracks are triangulated
@@ -320,7 +341,8 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
             cams[b, :3] = _angle_axis(R)
             cams[b, 3:6] = t
             pts, st = (t.cpu().numpy() for t in
-                       _triangulate(ctx, cams, intr, [a, b], common, rec.obs_d, n_tr))
+                       _triangulate(ctx, cams, intr, [a, b], common, rec.obs_d, n_tr,
+                                    robust_thr=max_err if robust else None)[:2])
             good = int(np.sum((st[:, 3] == 0) & (st[:, 0] < max_err)))
             if best is None or good > best[0]:
                 best = (good, cams, pts, st)
@@ -419,7 +441,8 @@ def _initial_pair_by_pose(rec, ctx, gb, pairs, pairs_t, cand, intr, n_tr, max_er
         cams[b, :3] = _angle_axis(Rs[j].reshape(3, 3))
         cams[b, 3:6] = ts[j]
         pts, st = (t.cpu().numpy() for t in
-                   _triangulate(ctx, cams, intr, [a, b], common, rec.obs_d, n_tr))
+                   _triangulate(ctx, cams, intr, [a, b], common, rec.obs_d, n_tr,
+                                robust_thr=max_err if rec.obs_ok_d is not None else None)[:2])
         good = int(np.sum((st[:, 3] == 0) & (st[:, 0] < max_err)))
         ok = (st[:, 3] == 0) & (st[:, 0] < max_err) & (st[:, 1] > 1.0)
         if good >= 30 and int(ok.sum()) >= 30:
@@ -434,10 +457,12 @@ def _initial_pair_by_pose(rec, ctx, gb, pairs, pairs_t, cand, intr, n_tr, max_er
             return
 
 
-def _triangulate(ctx, cams, intr, imgs, tracks, obs_d, n_tr):
+def _triangulate(ctx, cams, intr, imgs, tracks, obs_d, n_tr, robust_thr=None):
     """Triangulate `tracks` (ascending ids: host array or device tensor) from their observations
     in the images `imgs` (GPU kernel; the observations are selected on the device from obs_d =
-    (obs_track, timg, obs_xy)).  Returns device (pts [n, 3], stats [n, 4]) f64 tensors."""
+    (obs_track, timg, obs_xy)).  Returns device (pts [n, 3], stats [n, 4]) f64 tensors.
+    robust_thr (pixels): sfm_triangulate_robust keyed by the track ids instead; then returns
+    (pts, stats, o, mask): the observations used (indices into obs_d) and their conform flags."""
     import torch
     otr_d, timg_d, oxy_d = obs_d
     dev = otr_d.device
@@ -447,6 +472,12 @@ def _triangulate(ctx, cams, intr, imgs, tracks, obs_d, n_tr):
           torch.as_tensor(np.asarray(tracks, np.int64), device=dev))
     o, ptr = track_obs(otr_d, timg_d, n_tr, tr, in_img)
     T = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dt)).to(dev)
+    if robust_thr is not None:
+        pts, st, mask, _ = ctx.triangulate_robust(T(cams, np.float64), T(intr[:, 2:4], np.float64),
+                                                  ptr, timg_d[o].to(torch.int32),
+                                                  oxy_d[o].contiguous(), tr.to(torch.int32),
+                                                  thr=robust_thr)
+        return pts, st, o, mask
     return ctx.triangulate(T(cams, np.float64), T(intr[:, 2:4], np.float64), ptr,
                            timg_d[o].to(torch.int32), oxy_d[o].contiguous())
 
@@ -463,6 +494,17 @@ def _triangulate_new(rec, ctx, intr, max_err):
     n_reg.index_add_(0, sel, torch.ones_like(sel))
     todo_d = torch.nonzero(~rec.has_d & (n_reg >= 2)).squeeze(1)
     if todo_d.numel() == 0:
+        return
+    if rec.obs_ok_d is not None:
+        pts, st, o, mask = _triangulate(ctx, rec.cams, intr, np.nonzero(rec.registered)[0],
+                                        todo_d, rec.obs_d, n_tr, robust_thr=max_err)
+        ok = (st[:, 3] == 0) & (st[:, 0] < max_err) & (st[:, 1] > 1.0)
+        rec.pts_d[todo_d[ok]] = pts[ok]
+        rec.has_d[todo_d[ok]] = True
+        # an accepted track's observations (all in registered images) that its point excludes
+        acc = torch.zeros(n_tr, dtype=torch.bool, device=dev)
+        acc[todo_d] = ok
+        rec.obs_ok_d[o] = rec.obs_ok_d[o] & ~(acc[otr_d[o]] & (mask == 0))   # no sizing sync
         return
     pts, st = _triangulate(ctx, rec.cams, intr, np.nonzero(rec.registered)[0], todo_d, rec.obs_d,
                            n_tr)
@@ -484,7 +526,10 @@ def _bundle(rec, intr, loss_s, ba_iter, max_err, device, shard_ba=False, group=N
     otr_d, timg_d, oxy_d = rec.obs_d
     dev = otr_d.device
     reg_d = torch.from_numpy(rec.registered).to(dev)
-    use = torch.nonzero(reg_d[timg_d] & rec.has_d[otr_d]).squeeze(1)   # the one sizing sync
+    sel_d = reg_d[timg_d] & rec.has_d[otr_d]
+    if rec.obs_ok_d is not None:
+        sel_d &= rec.obs_ok_d
+    use = torch.nonzero(sel_d).squeeze(1)   # the one sizing sync
     n_use = int(use.shape[0])
     if n_use == 0:
         return
@@ -532,6 +577,14 @@ def _bundle(rec, intr, loss_s, ba_iter, max_err, device, shard_ba=False, group=N
     rec.pts_d[pts_ids] = pts
     mean = point_mean(err_d, first)
     rec.has_d[pts_ids[mean > max_err]] = False
+    if rec.obs_ok_d is not None:
+        # an observation the adjusted model still misses by more than max_err is no longer
+        # believed; a point left with fewer than two believed observations in registered
+        # images goes (all on the device: no sync)
+        rec.obs_ok_d[use] = ~(err_d > max_err)
+        n_ok = torch.zeros(rec.has_d.numel(), dtype=torch.int64, device=dev)
+        n_ok.index_add_(0, otr_d, (reg_d[timg_d] & rec.obs_ok_d).to(torch.int64))
+        rec.has_d &= n_ok >= 2
     rec.ba_log[-1]["s"] = time.perf_counter() - t0   # setup + LM + reprojection filter
     rec.ba_log[-1]["select_s"] = t_sel
     rec.history.append((int(reg.sum()), int(rec.has_d.sum()),

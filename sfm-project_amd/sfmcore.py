@@ -29,7 +29,8 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_graph_expand", "sfm_match_batch_both", "sfm_ransac_wave_stops",
             "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
             "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
-            "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid"]
+            "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid", "sfm_triangulate_robust",
+            "sfm_triangulate_cam_table"]
 
 
 class SfmCoreError(RuntimeError):
@@ -63,6 +64,11 @@ class RansacParams(C.Structure):
 
 class TwoViewPoseParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("min_inliers", C.c_int32), ("wide_key", C.c_float)]
+
+
+class TriangulateRobustParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_hyp", C.c_int32), ("thr", C.c_double),
+                ("max_cos2", C.c_double), ("seed", C.c_uint64)]
 
 
 # stages of sfm_ba_solve_stage (include/sfmcore.h)
@@ -133,6 +139,9 @@ def load_library(path: str = LIB_PATH):
         L.sfm_register_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(RegisterParams),
                                          vp, vp, vp, vp]
         L.sfm_triangulate.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.sfm_triangulate_robust.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp,
+                                             C.POINTER(TriangulateRobustParams), vp, vp, vp, vp]
+        L.sfm_triangulate_cam_table.argtypes = [vp, i32, vp, vp, vp]
         L.sfm_tracks.argtypes = [vp, i32, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp]
         L.sfm_graph_offsets.argtypes = [vp, i32, vp, i32, vp]
         L.sfm_graph_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
@@ -147,6 +156,11 @@ def load_library(path: str = LIB_PATH):
 def angle_key(angle_deg) -> np.float32:
     """The f32 ray-angle key of an angle up to 90 degrees: sin^2 (two_view_pose_batch's wide_key)."""
     return np.float32(np.sin(np.deg2rad(float(angle_deg))) ** 2)
+
+
+def max_cos2_of(min_angle_deg) -> float:
+    """cos^2 of the smallest admissible ray angle (triangulate_robust's max_cos2)."""
+    return float(np.cos(np.deg2rad(float(min_angle_deg))) ** 2)
 
 
 def _check(rc: int):
@@ -630,6 +644,54 @@ class Context:
                                         _ptr(pt_ptr), _ptr(cam_idx), _ptr(uv), _ptr(pts),
                                         _ptr(stats)))
         return pts, stats
+
+    def triangulate_robust(self, cams, pp, pt_ptr, cam_idx, uv, pt_id, thr=4.0, min_angle_deg=1.0,
+                           max_hyp=64, seed=42):
+        """RANSAC over the view pairs of every track (sfm_triangulate_robust): inputs as
+        triangulate plus pt_id [n_pt] i32, the key of each track's sampler.  Returns device
+        (pts [n_pt,3] f64, stats [n_pt,4] f64 over the consensus set, mask [n_obs] u8, info
+        [n_pt,2] i32 = consensus size, winning hypothesis); see include/sfmcore.h."""
+        torch = self.torch
+        n_pt = pt_ptr.shape[0] - 1
+        _expect("triangulate_robust", ("cams", cams, torch.float64, (8,)),
+                ("pp", pp, torch.float64, (2,)), ("pt_ptr", pt_ptr, torch.int32, ()),
+                ("cam_idx", cam_idx, torch.int32, ()), ("uv", uv, torch.float64, (2,)),
+                ("pt_id", pt_id, torch.int32, ()))
+        if pp.shape[0] != cams.shape[0] or uv.shape[0] != cam_idx.shape[0]:
+            raise SfmCoreError("triangulate_robust: cams / pp or cam_idx / uv sizes differ")
+        if pt_id.shape[0] != max(n_pt, 0):
+            raise SfmCoreError("triangulate_robust: pt_id must have one entry per track")
+        if not 0.0 <= float(min_angle_deg) < 90.0:
+            raise SfmCoreError("triangulate_robust: min_angle_deg must lie in [0, 90)")
+        n_obs = cam_idx.shape[0]
+        dev = cams.device
+        pts = torch.empty((max(n_pt, 0), 3), dtype=torch.float64, device=dev)
+        stats = torch.empty((max(n_pt, 0), 4), dtype=torch.float64, device=dev)
+        # observations outside every track's CSR range are never written: start from zero
+        mask = torch.zeros(n_obs, dtype=torch.uint8, device=dev)
+        info = torch.empty((max(n_pt, 0), 2), dtype=torch.int32, device=dev)
+        prm = TriangulateRobustParams(C.sizeof(TriangulateRobustParams), int(max_hyp), float(thr),
+                                      max_cos2_of(min_angle_deg), int(seed))
+        self._bind_stream()
+        _check(self.lib.sfm_triangulate_robust(self.handle, cams.shape[0], _ptr(cams), _ptr(pp),
+                                               n_pt, _ptr(pt_ptr), _ptr(cam_idx), _ptr(uv),
+                                               _ptr(pt_id), C.byref(prm), _ptr(pts), _ptr(stats),
+                                               _ptr(mask), _ptr(info)))
+        return pts, stats, mask, info
+
+    def triangulate_cam_table(self, cams, pp):
+        """The per-camera table [n_cam, 20] f64 the triangulation kernels start from
+        (sfm_triangulate_cam_table)."""
+        torch = self.torch
+        _expect("triangulate_cam_table", ("cams", cams, torch.float64, (8,)),
+                ("pp", pp, torch.float64, (2,)))
+        if pp.shape[0] != cams.shape[0]:
+            raise SfmCoreError("triangulate_cam_table: cams / pp sizes differ")
+        tab = torch.empty((cams.shape[0], 20), dtype=torch.float64, device=cams.device)
+        self._bind_stream()
+        _check(self.lib.sfm_triangulate_cam_table(self.handle, cams.shape[0], _ptr(cams),
+                                                  _ptr(pp), _ptr(tab)))
+        return tab
 
     def ba_solve(self, lin, cam_idx, pt_idx, pt_ptr, cam_ptr, cam_obs, lam, max_iter=100,
                  tol=1e-10, out=None, poll=8, poll_first=0):
