@@ -533,6 +533,36 @@ int sfm_orb_batch(sfm_ctx* ctx, const uint8_t* images, int32_t n_img, int32_t H,
                   const sfm_orb_params* prm, float* out_kp, uint8_t* out_desc,
                   int32_t* out_count);
 
+/* ---- image retrieval: vocabulary words, term frequencies, nearest images -------
+ * Pair selection for collections where most image pairs share nothing.  L2 / 128-byte descriptors
+ * only (Hamming vocabularies are out of scope).  Everything is integer and exact: the outputs are
+ * a function of the inputs alone.
+ *
+ * sfm_vocab_assign: the nearest vocabulary word of every descriptor by exact squared L2, the
+ * lowest word index among equal distances (i8 MFMA, the same contraction as sfm_match_batch).
+ *   desc      [n_img][k_max][128] u8 and n_kp [n_img] as for sfm_match_batch, k_max <= 8192
+ *   vocab     [n_words][128] u8, 1 <= n_words <= 65536
+ *   out_word  [n_img][k_max] i32: the word; -1 from n_kp[i] on
+ *   out_dist  [n_img][k_max] i32 or NULL: that d^2; 0 where the word is -1
+ *
+ * sfm_bow_hist: out_hist [n_img][n_words] u16 term frequencies of word [n_img][k_max] (entries
+ * outside [0, n_words), -1 among them, and entries from n_kp[i] on are skipped).  The whole array
+ * is written.  n_words <= 65536, k_max <= 65535, n_img <= 65535.
+ *
+ * sfm_bow_neighbours: score(a, b) = sum_w min(hist[a][w], hist[b][w]) * weight[w] in exact int64,
+ * weight [n_words] i32 in [0, 65535] (the caller validates the range).  For every image a the
+ * up-to-k images b != a with the largest positive score, in descending score order, lower b first
+ * among equal scores: out_nbr [n_img][k] i32 padded with -1, out_score [n_img][k] i64 padded with
+ * 0.  k >= 1; k >= n_img just pads.  Uses a dense [n_img][n_img] i64 score matrix in the
+ * context's workspace. */
+int sfm_vocab_assign(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, int32_t n_img,
+                     int32_t k_max, const uint8_t* vocab, int32_t n_words, int32_t* out_word,
+                     int32_t* out_dist);
+int sfm_bow_hist(sfm_ctx* ctx, const int32_t* word, const int32_t* n_kp, int32_t n_img,
+                 int32_t k_max, int32_t n_words, uint16_t* out_hist);
+int sfm_bow_neighbours(sfm_ctx* ctx, const uint16_t* hist, int32_t n_img, int32_t n_words,
+                       const int32_t* weight, int32_t k, int32_t* out_nbr, int64_t* out_score);
+
 /* ---- measurement: the device's i8 matrix ceiling right now ------------------------------------
  * Not a reference interface: the bench line's calibration probe (bench.py "calib"), so that K1's
  * roofline fraction can be read against the ceiling of the box it ran on.  Every CU runs MFMA-only

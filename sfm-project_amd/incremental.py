@@ -21,6 +21,7 @@ import numpy as np
 
 import match_graph
 import reconstruction
+import retrieval as _retrieval
 import sfmcore
 
 
@@ -73,6 +74,7 @@ class Reconstruction:
         self.history = []
         self.ba_log = []           # per bundle adjustment: size, LM / CG iterations, PCG branch
         self.n_verified = 0        # rows of the verified match graph
+        self.pairs = None          # [P,2] i32 image pairs that were matched and verified
         self.obs_d = None          # device (obs_track, timg, obs_xy) of the track observations
         self.gauge = None          # (reference camera, scale camera) of the initial pair
         self._tracks_d = None      # device (ptr, img, kp) of the tracks; host copies on first use
@@ -232,7 +234,7 @@ def point_mean(err, first):
 def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max_err=4.0,
                 ba_iter=20, loss_s=2.0, device=0, log=None, group=None, shard_ba=False,
                 ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6, init_pair="inliers",
-                init_candidates=64, triangulation="dlt"):
+                init_candidates=64, triangulation="dlt", pairs=None, retrieval=None):
     """desc [n_img,K,D] u8, kps [n_img,K,2] pixels, n_kp [n_img], intr [n_img,4] = (f, k1, cx, cy).
     Returns a Reconstruction (cams [n_img,8], registered mask, points per track, track arrays).
     With torch.distributed initialised (one process per GPU, `group` or the default group) the
@@ -262,7 +264,14 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     rec.obs_ok_d / rec.obs_ok flag the observations still believed: one excluded by the
     triangulation's mask, or left above max_err by a bundle adjustment, stays out of the later
     adjustments, and a point with fewer than two believed observations in registered images is
-    dropped."""
+    dropped.
+    pairs: which image pairs are matched and verified.  None (the default): all of them.
+    "retrieval": the pairs retrieval.select_pairs picks from the descriptors (vocabulary words,
+    idf-weighted histogram intersection, each image's k best neighbours), with
+    `retrieval` a dict of its keyword arguments (k, n_words, seed, lloyd, vocab).  Or a caller's
+    integer [P,2] array with 0 <= a < b < n_img, brought to sorted unique order.  The list is
+    kept as rec.pairs and the time it took as rec.timings["select_pairs"]; it is deterministic,
+    so under torch.distributed every rank computes the same list itself."""
     import time
     import torch
     if init_pair not in ("inliers", "pose"):
@@ -285,7 +294,17 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     tk = time.perf_counter()
     n_img = len(desc)
     intr = np.asarray(intr, np.float64)
-    pairs = np.stack(np.triu_indices(n_img, 1), axis=1).astype(np.int32)  # (a < b), a-major
+    if pairs is None:
+        pairs = np.stack(np.triu_indices(n_img, 1), axis=1).astype(np.int32)  # (a < b), a-major
+    else:
+        if isinstance(pairs, str):
+            if pairs != "retrieval":
+                raise ValueError(f"reconstruct: pairs must be None, 'retrieval' or a [P, 2] array, "
+                                 f"got {pairs!r}")
+            pairs = _retrieval.select_pairs(desc, n_kp, device=device, **(retrieval or {}))
+        else:
+            pairs = _retrieval.check_pairs(pairs, n_img)
+        tk = lap("select_pairs", tk)
     gb = match_graph.GraphBuilder(desc, kps, n_kp, device=device)
     pairs_t = torch.from_numpy(pairs).to(dev)
     rows, inl = _match_graph(gb, pairs, pairs_t, n_kp, group)
@@ -306,6 +325,7 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     rec.obs_d = obs_d
     rec.timings = tim
     rec.n_verified = int(rows.shape[0])
+    rec.pairs = pairs
     rec._tracks_d = (ptr_t, timg_t, tkp_t)
     tk = lap("tracks", tk)
     rec.pts_d = torch.zeros((n_tr, 3), dtype=torch.float64, device=dev)

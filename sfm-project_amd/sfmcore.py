@@ -30,7 +30,8 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_ba_set_chunks", "sfm_ba_chunk_tree", "sfm_ba_set_schur", "sfm_calib_mfma_i8",
             "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
             "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid", "sfm_triangulate_robust",
-            "sfm_triangulate_cam_table"]
+            "sfm_triangulate_cam_table", "sfm_vocab_assign", "sfm_bow_hist",
+            "sfm_bow_neighbours"]
 
 
 class SfmCoreError(RuntimeError):
@@ -147,6 +148,9 @@ def load_library(path: str = LIB_PATH):
         L.sfm_graph_rows.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
         L.sfm_graph_rows_packed.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
         L.sfm_graph_expand.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+        L.sfm_vocab_assign.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+        L.sfm_bow_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+        L.sfm_bow_neighbours.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
         for name in EXPORTED:
             getattr(L, name).restype = getattr(L, name).restype or C.c_int
         _lib = L
@@ -270,6 +274,79 @@ class Context:
         _check(self.lib.sfm_match_batch_both(self.handle, _ptr(desc), _ptr(n_kp), n_img, k_max,
                                              dim, _ptr(pairs), P, C.byref(prm), _ptr(out[0]),
                                              _ptr(out[1]), _ptr(out[2])))
+        return out
+
+    # ---- image retrieval --------------------------------------------------------------------
+    def vocab_assign(self, desc, n_kp, vocab, with_dist=True, out=None):
+        """Nearest vocabulary word of every descriptor (sfm_vocab_assign): desc [n_img,k_max,128]
+        u8, n_kp [n_img] i32, vocab [n_words,128] u8.  Returns (word [n_img,k_max] i32, -1 from
+        n_kp[i] on; dist [n_img,k_max] i32 squared L2, or None with with_dist=False)."""
+        torch = self.torch
+        _expect("vocab_assign", ("desc", desc, torch.uint8, (desc.shape[1], 128)),
+                ("n_kp", n_kp, torch.int32, ()), ("vocab", vocab, torch.uint8, (128,)))
+        n_img, k_max = desc.shape[0], desc.shape[1]
+        if n_kp.shape[0] != n_img:
+            raise SfmCoreError("vocab_assign: desc / n_kp sizes differ")
+        if out is None:
+            out = (torch.empty((n_img, k_max), dtype=torch.int32, device=desc.device),
+                   torch.empty((n_img, k_max), dtype=torch.int32, device=desc.device)
+                   if with_dist else None)
+        specs = [("out word", out[0], torch.int32, (k_max,))]
+        if out[1] is not None:
+            specs.append(("out dist", out[1], torch.int32, (k_max,)))
+        _expect("vocab_assign", *specs)
+        if any(o.shape[0] != n_img for _, o, _, _ in specs):
+            raise SfmCoreError("vocab_assign: out sizes differ from desc")
+        self._bind_stream()
+        _check(self.lib.sfm_vocab_assign(self.handle, _ptr(desc), _ptr(n_kp), n_img, k_max,
+                                         _ptr(vocab), vocab.shape[0], _ptr(out[0]),
+                                         _ptr(out[1]) if out[1] is not None else None))
+        return out
+
+    def bow_hist(self, word, n_kp, n_words, out=None):
+        """Term frequencies (sfm_bow_hist): word [n_img,k_max] i32, n_kp [n_img] i32.  Returns
+        hist [n_img,n_words] u16 (entries of -1 are skipped)."""
+        torch = self.torch
+        _expect("bow_hist", ("word", word, torch.int32, (word.shape[1],)),
+                ("n_kp", n_kp, torch.int32, ()))
+        n_img, k_max = word.shape
+        if n_kp.shape[0] != n_img:
+            raise SfmCoreError("bow_hist: word / n_kp sizes differ")
+        if out is None:
+            out = torch.empty((n_img, int(n_words)), dtype=torch.uint16, device=word.device)
+        _expect("bow_hist", ("out", out, torch.uint16, (int(n_words),)))
+        if out.shape[0] != n_img:
+            raise SfmCoreError("bow_hist: out size differs from word")
+        self._bind_stream()
+        _check(self.lib.sfm_bow_hist(self.handle, _ptr(word), _ptr(n_kp), n_img, k_max,
+                                     int(n_words), _ptr(out)))
+        return out
+
+    def bow_neighbours(self, hist, weight, k, out=None):
+        """Top-k images by weighted histogram intersection (sfm_bow_neighbours): hist
+        [n_img,n_words] u16, weight [n_words] i32 in [0, 65535].  Returns (nbr [n_img,k] i32
+        padded with -1, score [n_img,k] i64 padded with 0)."""
+        torch = self.torch
+        _expect("bow_neighbours", ("hist", hist, torch.uint16, (hist.shape[1],)),
+                ("weight", weight, torch.int32, ()))
+        n_img, n_words = hist.shape
+        k = int(k)
+        if weight.shape[0] != n_words:
+            raise SfmCoreError("bow_neighbours: hist / weight sizes differ")
+        if k < 1:
+            raise SfmCoreError("bow_neighbours: k must be >= 1")
+        if n_words and (int(weight.min().item()) < 0 or int(weight.max().item()) > 65535):
+            raise SfmCoreError("bow_neighbours: weight must lie in [0, 65535]")
+        if out is None:
+            out = (torch.empty((n_img, k), dtype=torch.int32, device=hist.device),
+                   torch.empty((n_img, k), dtype=torch.int64, device=hist.device))
+        _expect("bow_neighbours", ("out nbr", out[0], torch.int32, (k,)),
+                ("out score", out[1], torch.int64, (k,)))
+        if out[0].shape[0] != n_img or out[1].shape[0] != n_img:
+            raise SfmCoreError("bow_neighbours: out sizes differ from hist")
+        self._bind_stream()
+        _check(self.lib.sfm_bow_neighbours(self.handle, _ptr(hist), n_img, n_words, _ptr(weight),
+                                           k, _ptr(out[0]), _ptr(out[1])))
         return out
 
     # ---- feature extraction ----------------------------------------------------------------
