@@ -1,7 +1,7 @@
 """50-digit references for the steps after the match graph (test infrastructure, mpmath).
 
 Written from the specs in the kernel headers (csrc/camera_model.h, csrc/triangulate.hip,
-csrc/ba.hip), not from the kernels: every quantity is formed in 50-digit arithmetic from the
+csrc/ba.hip, csrc/two_view_pose.hip), not from the kernels: every quantity is formed in 50-digit arithmetic from the
 float64 inputs, so the only error a comparison charges to the code under test is its own.
 
   rotmat(r)                                   Rodrigues; the spec's first-order form for |r|^2 <= 1e-20
@@ -21,6 +21,13 @@ float64 inputs, so the only error a comparison charges to the code under test is
                                               implicit S x, solve_residual, solve_backsub,
                                               solve_direct, model_terms and the units of each
   solve_f64(...)                              float64 restatement of the solve with a mut switch
+  undistort_exact(xd, k1)                     the true inverse of the radial distortion, its
+                                              contraction factor; undistort_steps: the spec's steps
+  pose_normal(x1, x2, mask)                   the essential fit (csrc/two_view_pose.hip): exact N, its
+                                              eigenvalues and null vector, the null vector of A
+  pose_decompose(E)                           SVD of a float64 E, the four (R, t), status 2
+  pose_vote(R, t, x1, x2, mask)               depth numerators and ray-angle keys with their units
+  pose_f64(x1, x2, mask, mut)                 float64 restatement of the pose spec with a mut switch
 """
 from __future__ import annotations
 
@@ -941,3 +948,417 @@ def solve_f64(U, V, W, gc, gp, cam_idx, pt_idx, lam, max_iter=100, tol=1e-10, mu
     if mut == "h" and broke:
         rel = 0.0
     return x, dp, np.array([it, rel, gd, qq, flag], np.float64)
+
+
+# ---- two-view relative pose -----------------------------------------------------------------------
+# Spec (header of csrc/two_view_pose.hip): undistorted coordinates by 10 fixed-point
+# steps; N = A^T A over the inliers, E its null vector; the four (R, t) from E's SVD; the depth
+# numerators l1 = (a.b)(b.t) - (a.t)(b.b), l2 = (a.a)(b.t) - (a.b)(a.t) with a = R (x1, 1),
+# b = (x2, 1); the key s = |a x b|^2 / ((a.a)(b.b)) for a.b >= 0, else 2 - s, rounded to float32.
+# Every function takes float64 inputs, so a comparison charges the code only with its own error.
+
+POSE_TINY = 1e-8
+POSE_SWEEPS = 30
+
+
+@_hp
+def undistort_exact(xd, k1):
+    """The true inverse of x (1 + k1 |x|^2) = xd: (x [2] of mpf, rho), rho = |2 k1 r^2 / (1 + k1 r^2)|
+    the contraction factor of the fixed-point map x <- xd / (1 + k1 |x|^2) at the solution; (None,
+    None) where no inverse exists (k1 < 0 and |xd| beyond the fold 2 / (3 sqrt(-3 k1))).  Newton on
+    the radial cubic r + k1 r^3 = |xd| from the side on which it converges monotonically; of the
+    roots for k1 < 0 the one on the branch through the origin."""
+    xd = _vec(xd)
+    k1 = mp.mpf(float(k1))
+    rd = mp.sqrt(xd[0] * xd[0] + xd[1] * xd[1])
+    if rd == 0:
+        return [mp.mpf(0), mp.mpf(0)], mp.mpf(0)
+    if k1 < 0:
+        rs = 1 / mp.sqrt(-3 * k1)
+        if rd > 2 * rs / 3:
+            return None, None
+        r = mp.mpf(0)           # concave: from the left
+    else:
+        r = rd                  # convex: from the right
+    for _ in range(200):
+        step = (r + k1 * r ** 3 - rd) / (1 + 3 * k1 * r * r)
+        r -= step
+        if abs(step) <= mp.mpf(10) ** (-DPS + 5) * rd:
+            break
+    rho = abs(2 * k1 * r * r / (1 + k1 * r * r))
+    return [xd[0] * r / rd, xd[1] * r / rd], rho
+
+
+@_hp
+def undistort_steps(xd, k1, n=UNDISTORT_ITERS):
+    """The spec's n fixed-point steps in 50 digits: (x [2] of mpf, unit), the unit being the
+    first-order float64 error of the same steps: u <- |dT/dr| u + eps |x| (2 + 3 |k1| r^2 / |s|)."""
+    xd = _vec(xd)
+    k1 = mp.mpf(float(k1))
+    x0, x1 = xd
+    u = mp.mpf(0)
+    for _ in range(n):
+        r2 = x0 * x0 + x1 * x1
+        s = 1 + k1 * r2
+        y0, y1 = xd[0] / s, xd[1] / s
+        ny = mp.sqrt(y0 * y0 + y1 * y1)
+        u = abs(2 * k1 * mp.sqrt(r2) * ny / s) * u + EPS * ny * (2 + 3 * abs(k1) * r2 / abs(s))
+        x0, x1 = y0, y1
+    return [x0, x1], float(u)
+
+
+def _pose_rows(x1, x2, mask):
+    x1 = np.asarray(x1, np.float64).reshape(-1, 2)
+    x2 = np.asarray(x2, np.float64).reshape(-1, 2)
+    on = np.ones(len(x1), bool) if mask is None else np.asarray(mask).astype(bool)[:len(x1)]
+    rows = []
+    for a, b in zip(_mpl(x1[on]), _mpl(x2[on])):
+        rows.append([b[0] * a[0], b[0] * a[1], b[0], b[1] * a[0], b[1] * a[1], b[1], a[0], a[1],
+                     mp.mpf(1)])
+    return rows
+
+
+@_hp
+def pose_normal(x1, x2, mask=None):
+    """The fit in 50 digits.  dict: N [9,9] (the exact sum, rounded; N_mp unrounded, T_mp the sums
+    of the absolute terms), unit [9,9] = eps sum |terms|,
+    lam [9] ascending eigenvalues of the exact N, gap = lam2 - lam1, e [9] its null vector (mpf);
+    sv [9] ascending singular values of A itself, sgap = sv2 - sv1, a_null [9] A's null vector
+    (mp.svd_r; fewer than nine rows are padded with zero rows)."""
+    rows = _pose_rows(x1, x2, mask)
+    N, T = mp.zeros(9, 9), mp.zeros(9, 9)
+    for r in rows:
+        for i in range(9):
+            for j in range(i, 9):
+                N[i, j] += r[i] * r[j]
+                T[i, j] += abs(r[i] * r[j])
+    for i in range(9):
+        for j in range(i):
+            N[i, j], T[i, j] = N[j, i], T[j, i]
+    ev, Q = mp.eigsy(N)
+    order = sorted(range(9), key=lambda k: ev[k])
+    lam = [ev[k] for k in order]
+    A = mp.matrix(rows + [[0] * 9] * max(0, 9 - len(rows)))
+    _, S, V = mp.svd_r(A, full_matrices=False, compute_uv=True)
+    so = sorted(range(9), key=lambda k: S[k])
+    sv = [S[k] for k in so]
+    f = lambda M: np.array([[float(M[i, j]) for j in range(9)] for i in range(9)])
+    return dict(N=f(N), unit=EPS * f(T), N_mp=N, T_mp=T, lam=np.array([float(x) for x in lam]),
+                gap=float(lam[1] - lam[0]), e=[Q[i, order[0]] for i in range(9)],
+                sv=np.array([float(x) for x in sv]), sgap=float(sv[1] - sv[0]),
+                a_null=[V[so[0], j] for j in range(9)])
+
+
+@_hp
+def normal_ratio(N, ref):
+    """Worst |N - exact N| / (eps sum |terms|) over the entries of a float64 N [9,9]; ref from
+    pose_normal.  An entry without terms must be exactly zero."""
+    N = np.asarray(N, np.float64).reshape(9, 9)
+    worst = mp.mpf(0)
+    for i in range(9):
+        for j in range(9):
+            if not np.isfinite(N[i, j]):
+                return np.inf
+            d, u = abs(mp.mpf(float(N[i, j])) - ref["N_mp"][i, j]), EPS * ref["T_mp"][i, j]
+            if u == 0:
+                if d != 0:
+                    return np.inf
+                continue
+            worst = max(worst, d / u)
+    return float(worst)
+
+
+@_hp
+def norm_minus_1(v):
+    v = _vec(np.asarray(v, np.float64).ravel())
+    return float(mp.sqrt(sum(x * x for x in v)) - 1)
+
+
+@_hp
+def orth_defect(R, t):
+    """max(|R^T R - I|, |det R - 1|, ||t| - 1|) of a float64 (R [9], t [3]), formed in 50 digits."""
+    R = _mpl(np.asarray(R, np.float64).reshape(3, 3))
+    d = max(abs(sum(R[k][i] * R[k][j] for k in range(3)) - (1 if i == j else 0))
+            for i in range(3) for j in range(3))
+    c = _cross(R[1], R[2])
+    det = R[0][0] * c[0] + R[0][1] * c[1] + R[0][2] * c[2]
+    return float(max(d, abs(det - 1), abs(norm_minus_1(t))))
+
+
+@_hp
+def key_bracket(key_mp, half):
+    """(lo, hi) f32 arrays: the exact keys minus / plus `half`, each rounded once to float32."""
+    lo = np.array([_to_f32(k - mp.mpf(float(h))) for k, h in zip(key_mp, half)], np.float32)
+    hi = np.array([_to_f32(k + mp.mpf(float(h))) for k, h in zip(key_mp, half)], np.float32)
+    return lo, hi
+
+
+@_hp
+def undistort_compare(xd, k1, x, x_numpy, f=1000.0):
+    """One keypoint: the spec's output x (float64) and a plain numpy run of the same steps against
+    undistort_steps and undistort_exact.  dict exists, rho, px (|x - exact| f), steps (|x - steps| /
+    its unit), exact and numpy (|. - exact| / ((eps + rho^10) |x|))."""
+    xs, us = undistort_steps(xd, k1)
+    xe, rho = undistort_exact(xd, k1)
+    dist = lambda a, b: mp.sqrt((mp.mpf(float(a[0])) - b[0]) ** 2 + (mp.mpf(float(a[1])) - b[1]) ** 2)
+    ds = dist(x, xs)
+    out = dict(exists=xe is not None, rho=float(rho) if xe is not None else np.nan,
+               steps=float(ds / us) if us > 0 else (0.0 if ds == 0 else np.inf),
+               px=np.nan, exact=np.nan, numpy=np.nan)
+    if xe is not None:
+        nx = mp.sqrt(xe[0] ** 2 + xe[1] ** 2)
+        unit = (EPS + rho ** UNDISTORT_ITERS) * nx
+        de, dn = dist(x, xe), dist(x_numpy, xe)
+        out["px"] = float(de * f)
+        out["exact"] = float(de / unit) if unit > 0 else (0.0 if de == 0 else np.inf)
+        out["numpy"] = float(dn / unit) if unit > 0 else (0.0 if dn == 0 else np.inf)
+    return out
+
+
+def vec_dist(v, ref):
+    """max |v -+ ref| up to sign; v float64, ref a list of mpf."""
+    with mp.workdps(DPS):
+        v = _vec(np.asarray(v, np.float64).ravel())
+        return float(min(max(abs(a - b) for a, b in zip(v, ref)),
+                         max(abs(a + b) for a, b in zip(v, ref))))
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+@_hp
+def pose_decompose(E):
+    """50-digit SVD of a float64 E [9] and the spec's four candidates.  dict: sigma [3] descending,
+    cands = [(R 3x3 of mpf, t [3] of mpf)] x 4 (as a set: the order depends on the signs of the
+    singular vectors), status2 (a column norm of U at or below POSE_TINY), unit = eps sigma1 /
+    (sigma2 - sigma3), the conditioning of R and t."""
+    M = mp.matrix(3, 3)
+    for i, x in enumerate(np.asarray(E, np.float64).ravel()):
+        M[i // 3, i % 3] = mp.mpf(float(x))
+    U, S, V = mp.svd_r(M, full_matrices=True, compute_uv=True)
+    o = sorted(range(3), key=lambda k: -S[k])
+    sg = [S[k] for k in o]
+    v1, v2 = [V[o[0], j] for j in range(3)], [V[o[1], j] for j in range(3)]
+    u1, u2 = [U[i, o[0]] for i in range(3)], [U[i, o[1]] for i in range(3)]
+    v3, u3 = _cross(v1, v2), _cross(u1, u2)
+    Ra = [[u2[i] * v1[j] - u1[i] * v2[j] + u3[i] * v3[j] for j in range(3)] for i in range(3)]
+    Rb = [[u1[i] * v2[j] - u2[i] * v1[j] + u3[i] * v3[j] for j in range(3)] for i in range(3)]
+    neg = [-x for x in u3]
+    gap = sg[1] - sg[2]
+    return dict(sigma=np.array([float(x) for x in sg]),
+                cands=[(Ra, u3), (Ra, neg), (Rb, u3), (Rb, neg)],
+                status2=bool(sg[0] <= POSE_TINY or sg[1] <= POSE_TINY),
+                unit=float(EPS * sg[0] / gap) if gap > 0 else np.inf)
+
+
+def pose_dist(R, t, cands):
+    """Distance of a float64 (R, t) from the nearest 50-digit candidate: max over the 12 entries."""
+    with mp.workdps(DPS):
+        R, t = _vec(np.asarray(R, np.float64).ravel()), _vec(t)
+        best = None
+        for Rc, tc in cands:
+            d = max(max(abs(R[3 * i + j] - Rc[i][j]) for i in range(3) for j in range(3)),
+                    max(abs(t[i] - tc[i]) for i in range(3)))
+            best = d if best is None or d < best else best
+        return float(best)
+
+
+def pose_vote(R, t, x1, x2, mask=None):
+    """Per masked-in match under a float64 (R, t), in 50 digits: dict of float64 arrays l1, l2, ab,
+    key (exact, rounded to float64; key_mp unrounded), key32 (rounded once to float32), and the first-order
+    float64 error units u_l1, u_l2, u_key (eps times the sum of the absolute terms, hp_ref.VU),
+    front (both numerators > 0)."""
+    x1 = np.asarray(x1, np.float64).reshape(-1, 2)
+    x2 = np.asarray(x2, np.float64).reshape(-1, 2)
+    on = np.ones(len(x1), bool) if mask is None else np.asarray(mask).astype(bool)[:len(x1)]
+    x1, x2 = x1[on], x2[on]
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    t = np.asarray(t, np.float64)
+    n = len(x1)
+    # units: the float64 evaluation with exact inputs
+    c = lambda v: VU(np.full(n, float(v)))
+    p, q = [VU(x1[:, 0]), VU(x1[:, 1])], [VU(x2[:, 0]), VU(x2[:, 1]), c(1.0)]
+    a = [vsum([c(R[i, 0]) * p[0], c(R[i, 1]) * p[1], c(R[i, 2])]) for i in range(3)]
+    tv = [c(t[i]) for i in range(3)]
+    dot = lambda u, v: vsum([u[0] * v[0], u[1] * v[1], u[2] * v[2]])
+    aa, bb, ab, at, bt = dot(a, a), dot(q, q), dot(a, q), dot(a, tv), dot(q, tv)
+    l1 = vsum([ab * bt, -(at * bb)])
+    l2 = vsum([aa * bt, -(ab * at)])
+    cr = [vsum([a[1] * q[2], -(a[2] * q[1])]), vsum([a[2] * q[0], -(a[0] * q[2])]),
+          vsum([a[0] * q[1], -(a[1] * q[0])])]
+    s = dot(cr, cr) / (aa * bb)
+    u_key = np.where(ab.v >= 0.0, s.u, s.u + EPS * np.abs(2.0 - s.v))
+    out = dict(u_l1=l1.u, u_l2=l2.u, u_key=u_key)
+    ex = {k: np.zeros(n) for k in ("l1", "l2", "ab", "key")}
+    k32, key_mp = np.zeros(n, np.float32), []
+    with mp.workdps(DPS):
+        Rm, tm = _mpl(R), _mpl(t)
+        for m, (xa, xb) in enumerate(zip(_mpl(x1), _mpl(x2))):
+            am = [Rm[i][0] * xa[0] + Rm[i][1] * xa[1] + Rm[i][2] for i in range(3)]
+            bm = [xb[0], xb[1], mp.mpf(1)]
+            d = lambda u, v: u[0] * v[0] + u[1] * v[1] + u[2] * v[2]
+            maa, mbb, mab, mat, mbt = d(am, am), d(bm, bm), d(am, bm), d(am, tm), d(bm, tm)
+            cm = _cross(am, bm)
+            ms = d(cm, cm) / (maa * mbb)
+            key = ms if mab >= 0 else 2 - ms
+            ex["l1"][m], ex["l2"][m] = float(mab * mbt - mat * mbb), float(maa * mbt - mab * mat)
+            ex["ab"][m], ex["key"][m] = float(mab), float(key)
+            k32[m] = _to_f32(key)
+            key_mp.append(key)
+    out.update(ex)
+    out["key_mp"] = key_mp
+    out["key32"] = k32
+    out["front"] = (ex["l1"] > 0) & (ex["l2"] > 0)
+    return out
+
+
+def _to_f32(x):
+    """An mpf rounded ONCE to float32 (not through float64: no double rounding)."""
+    if x == 0:
+        return np.float32(0.0)
+    with mp.workprec(24):
+        y = +x
+    return np.float32(float(y))
+
+
+# Float64 restatement of the whole spec (numpy, written from DESIGN §4.2b), with the mutations of the
+# mutation check in tests/test_two_view_pose_hp_cpu.py; mut is never set otherwise.
+POSE_MUTATIONS = dict(
+    a="Jacobi capped at 2 sweeps", b="the second-smallest eigenvector taken",
+    c="the sign rule of tt dropped for theta < 0", d="the Gram-Schmidt step of u2 skipped",
+    e="at and bt swapped in l2", f="the 2 - s branch dropped",
+    g="upper median for lower median", h="> turned into >= at wide_key")
+
+
+def _jacobi_f64(A, mut=""):
+    """Cyclic Jacobi in the spec's round-robin order: (diagonal, V)."""
+    A = np.array(A, np.float64)
+    n = len(A)
+    V = np.eye(n)
+    h = (n - 1) // 2
+    for _ in range(2 if mut == "a" else POSE_SWEEPS):
+        off = float((np.triu(A, 1) ** 2).sum())
+        tr = float(np.trace(A))
+        if off <= 1e-60 * tr * tr:
+            break
+        for r in range(n):
+            rot = []
+            for i in range(h):
+                a, b = (r + i + 1) % n, (r + n - i - 1) % n
+                p, q = min(a, b), max(a, b)
+                c, s = 1.0, 0.0
+                if abs(A[p, q]) > 1e-300:
+                    th = (A[q, q] - A[p, p]) / (2.0 * A[p, q])
+                    sg = 1.0 if (th >= 0.0 or mut == "c") else -1.0
+                    tt = sg / (abs(th) + np.sqrt(th * th + 1.0))
+                    c = 1.0 / np.sqrt(tt * tt + 1.0)
+                    s = tt * c
+                rot.append((p, q, c, s))
+            for p, q, c, s in rot:
+                for M in (A, V):
+                    mp_, mq_ = M[:, p].copy(), M[:, q].copy()
+                    M[:, p], M[:, q] = c * mp_ - s * mq_, s * mp_ + c * mq_
+            for p, q, c, s in rot:
+                rp, rq = A[p].copy(), A[q].copy()
+                A[p], A[q] = c * rp - s * rq, s * rp + c * rq
+    return np.diag(A).copy(), V
+
+
+def score_f64(R, t, x1, x2, mut=""):
+    """(l1, l2, key f32) of every match under (R, t), numpy float64 in the spec's order of
+    operations."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    a = [(R[i, 0] * x1[:, 0] + R[i, 1] * x1[:, 1]) + R[i, 2] for i in range(3)]
+    b = [x2[:, 0], x2[:, 1], np.ones(len(x2))]
+    dot = lambda u, v: (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]
+    aa, bb, ab = dot(a, a), dot(b, b), dot(a, b)
+    at, bt = dot(a, [t[0], t[1], t[2]]), dot(b, [t[0], t[1], t[2]])
+    l1 = ab * bt - at * bb
+    l2 = (aa * at - ab * bt) if mut == "e" else (aa * bt - ab * at)
+    c = [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+    s = dot(c, c) / (aa * bb)
+    key = s if mut == "f" else np.where(ab >= 0.0, s, 2.0 - s)
+    return l1, l2, key.astype(np.float32)
+
+
+def decompose_f64(E, mut=""):
+    """(Ra, Rb, u3, ok) of a float64 E [9] as the spec decomposes it."""
+    E = np.asarray(E, np.float64).reshape(3, 3)
+    G = np.zeros((3, 3))
+    for i in range(3):
+        for j in range(3):
+            G[i, j] = (E[0, i] * E[0, j] + E[1, i] * E[1, j]) + E[2, i] * E[2, j]
+    w, V = _jacobi_f64(G, mut)
+    i1 = 0
+    for k in (1, 2):
+        if w[k] > w[i1]:
+            i1 = k
+    i2 = 1 if i1 == 0 else 0
+    for k in range(i2 + 1, 3):
+        if k != i1 and w[k] > w[i2]:
+            i2 = k
+    v1, v2 = V[:, i1], V[:, i2]
+    v3 = np.cross(v1, v2)
+    u1, u2 = E @ v1, E @ v2
+    n1 = np.sqrt(u1 @ u1)
+    if not n1 > POSE_TINY:
+        return None, None, None, False
+    u1 = u1 / n1
+    if mut != "d":
+        u2 = u2 - (u2 @ u1) * u1
+    n2 = np.sqrt(u2 @ u2)
+    if not n2 > POSE_TINY:
+        return None, None, None, False
+    u2 = u2 / n2
+    u3 = np.cross(u1, u2)
+    Ra = np.outer(u2, v1) - np.outer(u1, v2) + np.outer(u3, v3)
+    Rb = np.outer(u1, v2) - np.outer(u2, v1) + np.outer(u3, v3)
+    return Ra, Rb, u3, True
+
+
+def pose_f64(x1, x2, mask=None, mut="", min_inliers=8, wide_key=0.0):
+    """dict(E [9], R [9], t [3], stat [8], median_key f32, N [9,9], cand (Ra, Rb, u3)) as
+    tests/pose_ref.c returns them.  mut: a key of POSE_MUTATIONS."""
+    x1 = np.asarray(x1, np.float64).reshape(-1, 2)
+    x2 = np.asarray(x2, np.float64).reshape(-1, 2)
+    on = np.ones(len(x1), bool) if mask is None else np.asarray(mask).astype(bool)[:len(x1)]
+    x1, x2 = x1[on], x2[on]
+    n = len(x1)
+    out = dict(E=np.zeros(9), R=np.zeros(9), t=np.zeros(3), stat=np.zeros(8, np.int32),
+               median_key=np.float32(0.0), N=np.zeros((9, 9)), cand=None)
+    if n < max(min_inliers, 8):
+        out["stat"][0] = 1
+        return out
+    A = np.stack([x2[:, 0] * x1[:, 0], x2[:, 0] * x1[:, 1], x2[:, 0], x2[:, 1] * x1[:, 0],
+                  x2[:, 1] * x1[:, 1], x2[:, 1], x1[:, 0], x1[:, 1], np.ones(n)], 1)
+    N = np.zeros((9, 9))
+    for i in range(9):
+        for j in range(i, 9):
+            N[i, j] = N[j, i] = float(np.sum(A[:, i] * A[:, j]))
+    out["N"] = N
+    w, V = _jacobi_f64(N, mut)
+    order = np.argsort(w, kind="stable")
+    e = V[:, order[1] if mut == "b" else order[0]].copy()
+    Ra, Rb, u3, ok = decompose_f64(e, mut)
+    if not ok:
+        out["stat"][0] = 2
+        return out
+    out["cand"] = (Ra, Rb, u3)
+    nf, keys = [], []
+    for c in range(4):
+        Rc, tc = (Rb if c >> 1 else Ra), (-u3 if c & 1 else u3)
+        l1, l2, key = score_f64(Rc, tc, x1, x2, mut)
+        front = (l1 > 0.0) & (l2 > 0.0)
+        nf.append(int(front.sum()))
+        keys.append(np.sort(key[front]))
+    best = int(np.argmax(nf))
+    k = keys[best]
+    wk = np.float32(wide_key)
+    out["E"], out["R"] = e, (Rb if best >> 1 else Ra).ravel().copy()
+    out["t"] = (-u3 if best & 1 else u3).copy()
+    n_wide = int((k >= wk).sum() if mut == "h" else (k > wk).sum())
+    out["stat"][:] = [0, best, *nf, n_wide, n]
+    if len(k):
+        out["median_key"] = k[len(k) // 2 if mut == "g" else (len(k) - 1) // 2]
+    return out

@@ -260,23 +260,30 @@ void pref_pose(const double* x1, const double* x2, const uint8_t* mask, int32_t 
     stat[7] = n_inl;
 }
 
-/* The batch, with the arguments of sfm_two_view_pose_batch (host arrays). */
+/* The candidates of a fitted E: Ra, Rb [9], u3 [3] (candidate c = (c >> 1 ? Rb : Ra, c & 1 ? -u3 :
+ * u3)); returns 0 where pref_pose reports status 2 */
+int32_t pref_candidates(const double E[9], double Ra[9], double Rb[9], double u3[3]) {
+    return decompose(E, Ra, Rb, u3);
+}
+
+static int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+/* The batch, with the arguments of sfm_two_view_pose_batch (host arrays).  Image ids, match counts
+ * and keypoint indices are clamped to their arrays, as the kernels clamp them. */
 void pref_pose_batch(const float* kps, int32_t n_img, int32_t k_max, const int32_t* pairs,
                      int32_t P, const int32_t* match_count, const int32_t* matches,
                      const uint8_t* mask, const int32_t* inl_count, const double* intr,
                      int32_t min_inliers, float wide_key, double* E, double* R, double* t,
                      int32_t* stat, float* median_key) {
-    (void)n_img;
     double* x1 = (double*)malloc(sizeof(double) * 2 * (size_t)(k_max > 0 ? k_max : 1));
     double* x2 = (double*)malloc(sizeof(double) * 2 * (size_t)(k_max > 0 ? k_max : 1));
     for (int p = 0; p < P; ++p) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
-        int M = match_count[p];
-        M = M < 0 ? 0 : (M > k_max ? k_max : M);
+        const int a = clampi(pairs[2 * p], n_img - 1), b = clampi(pairs[2 * p + 1], n_img - 1);
+        const int M = clampi(match_count[p], k_max);
         const int32_t* mt = matches + (size_t)p * k_max * 2;
         for (int m = 0; m < M; ++m) {
-            const float* ka = kps + ((size_t)a * k_max + mt[2 * m]) * 2;
-            const float* kb = kps + ((size_t)b * k_max + mt[2 * m + 1]) * 2;
+            const float* ka = kps + ((size_t)a * k_max + clampi(mt[2 * m], k_max - 1)) * 2;
+            const float* kb = kps + ((size_t)b * k_max + clampi(mt[2 * m + 1], k_max - 1)) * 2;
             pref_undistort(ka[0], ka[1], intr + 4 * a, x1 + 2 * m);
             pref_undistort(kb[0], kb[1], intr + 4 * b, x2 + 2 * m);
         }

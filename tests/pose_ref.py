@@ -38,6 +38,8 @@ def lib():
         L.pref_normal_matrix.restype = None
         L.pref_pose.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp]
         L.pref_pose.restype = None
+        L.pref_candidates.argtypes = [vp, vp, vp, vp]
+        L.pref_candidates.restype = i32
         L.pref_pose_batch.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, f32, vp, vp,
                                       vp, vp, vp]
         L.pref_pose_batch.restype = None
@@ -83,6 +85,15 @@ def normal_matrix(x1, x2, mask=None) -> np.ndarray:
     N = np.zeros(81, np.float64)
     lib().pref_normal_matrix(_p(x1), _p(x2), _p(mk), M, _p(N))
     return N.reshape(9, 9)
+
+
+def candidates(E):
+    """(Ra [9], Rb [9], u3 [3], ok) of a fitted E [9]: candidate c is (Rb if c >> 1 else Ra,
+    -u3 if c & 1 else u3); ok is False where the pose reports status 2."""
+    E = np.ascontiguousarray(E, np.float64).ravel()
+    Ra, Rb, u3 = np.zeros(9), np.zeros(9), np.zeros(3)
+    ok = lib().pref_candidates(_p(E), _p(Ra), _p(Rb), _p(u3))
+    return Ra, Rb, u3, bool(ok)
 
 
 def _result(E, R, t, stat, med):
