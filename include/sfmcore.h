@@ -231,6 +231,47 @@ int sfm_two_view_pose_batch(sfm_ctx* ctx, const float* kps, int32_t n_img, int32
                             const sfm_two_view_pose_params* prm, double* out_E, double* out_R,
                             double* out_t, int32_t* out_stat, float* out_median_key);
 
+/* Guided matching (COLMAP's guided_matching): re-match verified pairs with the
+ * candidates restricted to the epipolar band of the pair's F.  L2 descriptors, dim == 128 only.
+ * tests/guided_ref.c states the spec; the outputs equal it byte for byte, whatever the batch.
+ *   desc, n_kp, n_img, k_max, dim, pairs, n_pairs   as sfm_match_batch (k_max <= 8192; any a, b in
+ *                                                   range, a == b included)
+ *   kps [n_img][k_max][2] f32                       pixel coordinates
+ *   inl_count [n_pairs] i32, F [n_pairs][9] f32, norm [n_pairs][6] f32
+ *                                                   as sfm_ransac_f_batch writes them
+ *   skip        a pair gets count 0 and a zero ncand row if inl_count < max(prm->min_inliers, 8),
+ *               n_kp[a] == 0, n_kp[b] == 0, s1 == 0 or s2 == 0 (norm = cx1, cy1, s1, cx2, cy2, s2)
+ *   candidate   cand(i, j) = K2's Sampson test at prm->thr on keypoint i of a and j of b: with
+ *               (k1, k2) = sampson_scales(s1, s2, thr), G = sampson_prep(F, k1, k2) and
+ *               X1 = ((x - cx1) s1) k1, ... (f32, each operation rounded), sampson_inlier(G, X1_i,
+ *               Y1_i, X2_j, Y2_j) of oracle/sfm_oracle_ransac.inc, the same FMA sequence; a NaN
+ *               anywhere gives false (a NaN in F: no candidates, count 0)
+ *   matching    sfm_match_batch's non-OpenCV rules on the d^2 matrix with the non-candidates
+ *               removed: nn[i] = the candidate of smallest d^2 (lowest j among equals); the ratio
+ *               test den^2 d1 < num^2 d2 against the second smallest value of the candidates'
+ *               distance multiset (fewer than two candidates: passes); SFM_XC_MUTUAL keeps i iff
+ *               the candidate query of smallest d^2 for nn[i] (lowest i among equals) is i;
+ *               max_dist >= 0 keeps d1 < max_dist.  A query with a single candidate passes the
+ *               ratio test, so callers should set max_dist.
+ *   out_count, out_match, out_dist   sfm_match_batch's layout (ascending queryIdx; entries from
+ *               count on are unspecified): they feed sfm_ransac_f_batch, sfm_graph_rows* and
+ *               sfm_two_view_pose_batch unchanged
+ *   out_ncand [n_pairs][k_max] i32   candidates of every query, 0 from n_kp[a] on; may be NULL */
+typedef struct sfm_guided_params {
+    int32_t struct_size;   /* sizeof(sfm_guided_params) of the caller, as sfm_two_view_pose_params */
+    int32_t cross_check;   /* SFM_XC_NONE or SFM_XC_MUTUAL (SFM_XC_OPENCV: SFM_ERR_INVALID) */
+    int32_t ratio_num, ratio_den;   /* den = 0: off */
+    int32_t min_inliers;
+    float   thr;           /* Sampson band in squared pixels, > 0 */
+    int64_t max_dist;      /* d^2 < max_dist; < 0: off */
+} sfm_guided_params;
+int sfm_guided_match_batch(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp,
+                           const float* kps, int32_t n_img, int32_t k_max, int32_t dim,
+                           const int32_t* pairs, int32_t n_pairs, const int32_t* inl_count,
+                           const float* F, const float* norm, const sfm_guided_params* prm,
+                           int32_t* out_count, int32_t* out_match, int32_t* out_dist,
+                           int32_t* out_ncand);
+
 /* ---- verified match graph -------------------------------------------------------------------
  * Replaces the pair_matches list of code/pipeline.py:42-47 (Pair(img_inx_1, img_inx_2, matches)
  * for every non-empty pair) for a batch: rows (pair_base + pair, queryIdx, trainIdx) of the RANSAC

@@ -257,6 +257,55 @@ def two_view_pose(kp1, kp2, matches, intr1, intr2, pair=(0, 1), n_hyp=DEFAULT_HY
     return res
 
 
+def guided_match_pair(kp1, kp2, des1, des2, pair=(0, 1), n_hyp=DEFAULT_HYPOTHESES,
+                      seed=DEFAULT_SEED, thr=DEFAULT_THRESHOLD, min_inliers=DEFAULT_MIN_INLIERS,
+                      guided=True, ratio=(4, 5), cross_check=sfmcore.XC_MUTUAL, max_dist=-1,
+                      device=0):
+    """Guided matching of one pair: match (ratio / cross_check / max_dist, as
+    match_graph.GraphBuilder), verify, re-match inside the epipolar band of the estimated F
+    (sfm_guided_match_batch; `guided` = True or a dict of thr, ratio, cross_check, max_dist over
+    match_graph.GUIDED_DEFAULTS) and verify again with the same seed.  kp1 / kp2 [K,2] pixels,
+    des1 / des2 [K,128] u8.  Equals GraphBuilder(guided=...).run on that pair.
+
+    Returns dict(F [3,3] pixel F of the second verification, matches [M,2] (queryIdx, trainIdx)
+    guided matches, dist [M] their d^2, inliers [n] indices into matches (ascending), count and
+    verified of the second verification, first_count the first verification's inlier count)."""
+    import torch
+    from match_graph import guided_options
+    gkw = guided_options(True if guided is None else guided)
+    if gkw is None:
+        raise ValueError("guided_match_pair: guided must be True or a dict of options")
+    k1, k2 = np.asarray(kp1, np.float32).reshape(-1, 2), np.asarray(kp2, np.float32).reshape(-1, 2)
+    d1, d2 = np.asarray(des1, np.uint8), np.asarray(des2, np.uint8)
+    if d1.shape != (len(k1), 128) or d2.shape != (len(k2), 128):
+        raise ValueError("guided_match_pair: descriptors must be [K, 128] u8, one per keypoint")
+    a, b = int(pair[0]), int(pair[1])
+    n_img, k_max = max(a, b) + 1, max(len(k1), len(k2), 1)
+    kps = np.zeros((n_img, k_max, 2), np.float32)
+    desc = np.zeros((n_img, k_max, 128), np.uint8)
+    n_kp = np.zeros(n_img, np.int32)
+    kps[a, :len(k1)], desc[a, :len(k1)], n_kp[a] = k1, d1, len(k1)
+    kps[b, :len(k2)], desc[b, :len(k2)], n_kp[b] = k2, d2, len(k2)
+    dev = torch.device("cuda", device)
+    ctx = sfmcore.context(device)
+    T = lambda x: torch.from_numpy(x).to(dev)
+    desc_d, kps_d, n_kp_d = T(desc), T(kps), T(n_kp)
+    pr = T(np.array([[a, b]], np.int32))
+    rkw = dict(n_hyp=n_hyp, seed=seed, thr=thr, min_inliers=min_inliers)
+    count, match, _ = ctx.match_batch(desc_d, n_kp_d, pr, metric=sfmcore.METRIC_L2,
+                                      cross_check=cross_check, ratio=ratio, max_dist=max_dist)
+    rs = ctx.ransac_batch(kps_d, pr, count, match, **rkw)
+    gcount, gmatch, gdist = ctx.guided_match_batch(desc_d, n_kp_d, kps_d, pr, rs["inl_count"],
+                                                   rs["F"], rs["norm"], min_inliers=min_inliers,
+                                                   **gkw)
+    rs2 = ctx.ransac_batch(kps_d, pr, gcount, gmatch, **rkw)
+    M = int(gcount.item())
+    cnt, _, Fn, norm, mask = _unpack(_pack(rs2, "F", M).cpu().numpy(), M)
+    return dict(F=denormalize_F(Fn, norm), matches=gmatch[0, :M].cpu().numpy(),
+                dist=gdist[0, :M].cpu().numpy(), inliers=np.nonzero(mask)[0], count=max(cnt, 0),
+                verified=cnt >= min_inliers, first_count=max(int(rs["inl_count"].item()), 0))
+
+
 def _match_array(matches) -> np.ndarray:
     if len(matches) and hasattr(matches[0], "queryIdx"):
         return np.array([[m.queryIdx, m.trainIdx] for m in matches], np.int32).reshape(-1, 2)

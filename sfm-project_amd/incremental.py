@@ -234,7 +234,8 @@ def point_mean(err, first):
 def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max_err=4.0,
                 ba_iter=20, loss_s=2.0, device=0, log=None, group=None, shard_ba=False,
                 ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6, init_pair="inliers",
-                init_candidates=64, triangulation="dlt", pairs=None, retrieval=None):
+                init_candidates=64, triangulation="dlt", pairs=None, retrieval=None,
+                guided=None):
     """desc [n_img,K,D] u8, kps [n_img,K,2] pixels, n_kp [n_img], intr [n_img,4] = (f, k1, cx, cy).
     Returns a Reconstruction (cams [n_img,8], registered mask, points per track, track arrays).
     With torch.distributed initialised (one process per GPU, `group` or the default group) the
@@ -271,7 +272,11 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     `retrieval` a dict of its keyword arguments (k, n_words, seed, lloyd, vocab).  Or a caller's
     integer [P,2] array with 0 <= a < b < n_img, brought to sorted unique order.  The list is
     kept as rec.pairs and the time it took as rec.timings["select_pairs"]; it is deterministic,
-    so under torch.distributed every rank computes the same list itself."""
+    so under torch.distributed every rank computes the same list itself.
+    guided: None (the default), True or a dict of thr / ratio / cross_check / max_dist: guided
+    matching (match_graph.GraphBuilder's `guided`).  Every verified pair is
+    re-matched inside the epipolar band of its F and verified again, and the graph is built from
+    the second verification."""
     import time
     import torch
     if init_pair not in ("inliers", "pose"):
@@ -305,7 +310,7 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
         else:
             pairs = _retrieval.check_pairs(pairs, n_img)
         tk = lap("select_pairs", tk)
-    gb = match_graph.GraphBuilder(desc, kps, n_kp, device=device)
+    gb = match_graph.GraphBuilder(desc, kps, n_kp, device=device, guided=guided)
     pairs_t = torch.from_numpy(pairs).to(dev)
     rows, inl = _match_graph(gb, pairs, pairs_t, n_kp, group)
     tk = lap("match_verify", tk)

@@ -40,12 +40,35 @@ def shard_pairs(pairs: np.ndarray, rank: int, world: int, n_kp=None) -> np.ndarr
     return np.asarray(pairs, np.int32)[lo:hi]
 
 
+# Guided matching defaults: a 4 px^2 Sampson band (2 px), Lowe 4/5 inside the band, the mutual
+# rule, and COLMAP's descriptor cap 0.7 on unit descriptors at this project's 512 scale,
+# (0.7 * 512)^2 = 128450.  The cap matters: a query with a single candidate in its band passes the
+# ratio test automatically.
+GUIDED_DEFAULTS = dict(thr=4.0, ratio=(4, 5), cross_check=sfmcore.XC_MUTUAL, max_dist=128450)
+
+
+def guided_options(guided):
+    """None for off (None / False), else GUIDED_DEFAULTS updated by the caller's dict."""
+    if guided is None or guided is False:
+        return None
+    kw = dict(GUIDED_DEFAULTS)
+    if guided is not True:
+        extra = set(guided) - set(kw)
+        if extra:
+            raise ValueError(f"guided: unknown option(s) {sorted(extra)}; known: {sorted(kw)}")
+        kw.update(guided)
+    return kw
+
+
 class GraphBuilder:
     """Holds one image set on the device and verifies pair batches against it."""
 
     def __init__(self, desc, kps, n_kp=None, device: int = 0, ratio=(4, 5),
                  cross_check=sfmcore.XC_MUTUAL, max_dist=-1, n_hyp=4096, seed=42, thr=1.0,
-                 min_inliers=15):
+                 min_inliers=15, guided=None):
+        """guided: None / False (the default: K1 + K2 only), True, or a dict of thr, ratio,
+        cross_check, max_dist overriding GUIDED_DEFAULTS: run() then re-matches every verified
+        pair inside the epipolar band of its F and verifies again."""
         import torch
         self.torch = torch
         self.dev = torch.device("cuda", device)
@@ -62,6 +85,9 @@ class GraphBuilder:
                              max_dist=max_dist)
         self.ransac_kw = dict(n_hyp=n_hyp, seed=seed, thr=thr, min_inliers=min_inliers)
         self.min_inliers = min_inliers
+        self.guided_kw = guided_options(guided)
+        if self.guided_kw is not None and self.metric != sfmcore.METRIC_L2:
+            raise ValueError("GraphBuilder: guided matching needs L2 (128-byte) descriptors")
         self._bufs = {}
 
     def _buffers(self, P):
@@ -96,10 +122,38 @@ class GraphBuilder:
         return self.ctx.ransac_batch(self.kps, pairs_t, count, match, out=b["ransac"],
                                      **self.ransac_kw)
 
+    def _guided_buffers(self, b, P):
+        """The second buffer set of a batch size (guided matches and their verification),
+        allocated the first time a guided run needs it."""
+        if "guided" not in b:
+            torch, dev, K = self.torch, self.dev, self.k_max
+            b["guided"] = (torch.empty(P, dtype=torch.int32, device=dev),
+                           torch.empty((P, K, 2), dtype=torch.int32, device=dev),
+                           torch.empty((P, K), dtype=torch.int32, device=dev))
+            b["guided_ransac"] = {k: torch.empty_like(v) for k, v in b["ransac"].items()}
+        return b["guided"], b["guided_ransac"]
+
+    def guided_match(self, pairs_t, rs):
+        """Guided matches of a batch from its first verification `rs` (sfm_guided_match_batch on
+        rs's F, norm and inl_count); a pair that did not verify gets count 0."""
+        b = self._buffers(pairs_t.shape[0])
+        out, _ = self._guided_buffers(b, pairs_t.shape[0])
+        return self.ctx.guided_match_batch(self.desc, self.n_kp, self.kps, pairs_t,
+                                           rs["inl_count"], rs["F"], rs["norm"], out=out,
+                                           min_inliers=self.min_inliers, **self.guided_kw)
+
     def run(self, pairs_t):
-        """K1 + K2 on one pair batch; returns (count, match, dist, ransac dict) device tensors."""
+        """K1 + K2 on one pair batch; returns (count, match, dist, ransac dict) device tensors.
+        With guided matching on: K1, K2, the guided re-match on K2's F, then K2 again on the
+        guided matches with the same seed and pair keys; the second pass's tensors are returned."""
         count, match, dist = self.match(pairs_t)
         rs = self.verify(pairs_t, count, match)
+        if self.guided_kw is None:
+            return count, match, dist, rs
+        count, match, dist = self.guided_match(pairs_t, rs)
+        b = self._buffers(pairs_t.shape[0])
+        rs = self.ctx.ransac_batch(self.kps, pairs_t, count, match, out=b["guided_ransac"],
+                                   **self.ransac_kw)
         return count, match, dist, rs
 
     def graph_rows(self, pair_base: int, count, match, rs, return_offsets=False, packed=False):

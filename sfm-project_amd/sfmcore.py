@@ -31,7 +31,7 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
             "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid", "sfm_triangulate_robust",
             "sfm_triangulate_cam_table", "sfm_vocab_assign", "sfm_bow_hist",
-            "sfm_bow_neighbours"]
+            "sfm_bow_neighbours", "sfm_guided_match_batch"]
 
 
 class SfmCoreError(RuntimeError):
@@ -65,6 +65,12 @@ class RansacParams(C.Structure):
 
 class TwoViewPoseParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("min_inliers", C.c_int32), ("wide_key", C.c_float)]
+
+
+class GuidedParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("cross_check", C.c_int32), ("ratio_num", C.c_int32),
+                ("ratio_den", C.c_int32), ("min_inliers", C.c_int32), ("thr", C.c_float),
+                ("max_dist", C.c_int64)]
 
 
 class TriangulateRobustParams(C.Structure):
@@ -118,6 +124,8 @@ def load_library(path: str = LIB_PATH):
                                           C.POINTER(RansacParams), vp, vp, vp]
         L.sfm_two_view_pose_batch.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp,
                                               C.POINTER(TwoViewPoseParams), vp, vp, vp, vp, vp]
+        L.sfm_guided_match_batch.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp,
+                                             C.POINTER(GuidedParams), vp, vp, vp, vp]
         L.sfm_ransac_stats.argtypes = [vp, i32, vp]
         L.sfm_ransac_wave_stops.argtypes = [vp, i32, i32, vp]
         L.sfm_match_cert_stats.argtypes = [vp, i32, vp]
@@ -510,6 +518,52 @@ class Context:
             self.handle, _ptr(kps), n_img, k_max, _ptr(pairs), P, _ptr(count), _ptr(match),
             _ptr(mask), _ptr(inl_count), _ptr(intr), C.byref(prm), _ptr(out["E"]), _ptr(out["R"]),
             _ptr(out["t"]), _ptr(out["stat"]), _ptr(out["median_key"])))
+        return out
+
+    def guided_match_batch(self, desc, n_kp, kps, pairs, inl_count, F, norm, thr=4.0,
+                           ratio=(4, 5), cross_check=XC_MUTUAL, max_dist=128450, min_inliers=15,
+                           with_ncand=False, out=None):
+        """Guided matching (sfm_guided_match_batch): re-match the verified pairs with the
+        candidates of every query restricted to the epipolar band (Sampson error < thr squared
+        pixels) of the pair's F.  desc [n_img,k_max,128] u8, n_kp [n_img] i32, kps [n_img,k_max,2]
+        f32, pairs [P,2] i32; inl_count [P] i32, F [P,9] f32 and norm [P,6] f32 as ransac_batch
+        returns them.  A pair with inl_count < max(min_inliers, 8) gets count 0.
+
+        max_dist defaults to (0.7 * 512)^2, COLMAP's 0.7 on unit descriptors at this project's
+        512 scale: a query with a single candidate in its band passes the ratio test
+        automatically, so the distance cap is what rejects it when it is wrong.
+
+        Returns (count [P], match [P,k_max,2], dist [P,k_max]) in match_batch's layout, and with
+        with_ncand a fourth tensor ncand [P,k_max] i32, the candidates of every query.  out: the
+        tuple to write into (3 tensors, or 4 with with_ncand)."""
+        torch = self.torch
+        n_img, k_max, dim = desc.shape
+        _expect("guided_match_batch", ("desc", desc, torch.uint8, (k_max, dim)),
+                ("n_kp", n_kp, torch.int32, ()), ("kps", kps, torch.float32, (k_max, 2)),
+                ("pairs", pairs, torch.int32, (2,)), ("inl_count", inl_count, torch.int32, ()),
+                ("F", F, torch.float32, (9,)), ("norm", norm, torch.float32, (6,)))
+        P = pairs.shape[0]
+        if kps.shape[0] != n_img or n_kp.shape[0] != n_img or not (
+                inl_count.shape[0] == F.shape[0] == norm.shape[0] == P):
+            raise SfmCoreError("guided_match_batch: kps / n_kp must have one row per image and "
+                               "inl_count / F / norm one per pair")
+        dev = desc.device
+        if out is None:
+            out = (torch.empty(P, dtype=torch.int32, device=dev),
+                   torch.empty((P, k_max, 2), dtype=torch.int32, device=dev),
+                   torch.empty((P, k_max), dtype=torch.int32, device=dev))
+            if with_ncand:
+                out = out + (torch.empty((P, k_max), dtype=torch.int32, device=dev),)
+        if len(out) != (4 if with_ncand else 3):
+            raise SfmCoreError("guided_match_batch: out must hold 3 tensors, 4 with with_ncand")
+        num, den = (0, 0) if ratio is None else ratio
+        prm = GuidedParams(C.sizeof(GuidedParams), int(cross_check), int(num), int(den),
+                           int(min_inliers), float(thr), int(max_dist))
+        self._bind_stream()
+        _check(self.lib.sfm_guided_match_batch(
+            self.handle, _ptr(desc), _ptr(n_kp), _ptr(kps), n_img, k_max, dim, _ptr(pairs), P,
+            _ptr(inl_count), _ptr(F), _ptr(norm), C.byref(prm), _ptr(out[0]), _ptr(out[1]),
+            _ptr(out[2]), _ptr(out[3]) if with_ncand else None))
         return out
 
     def ransac_stats(self, enable=True, read=False):
