@@ -575,9 +575,11 @@ int sfm_orb_batch(sfm_ctx* ctx, const uint8_t* images, int32_t n_img, int32_t H,
                   int32_t* out_count);
 
 /* ---- image retrieval: vocabulary words, term frequencies, nearest images -------
- * Pair selection for collections where most image pairs share nothing.  L2 / 128-byte descriptors
- * only (Hamming vocabularies are out of scope).  Everything is integer and exact: the outputs are
- * a function of the inputs alone.
+ * Pair selection for collections where most image pairs share nothing.  Word assignment exists
+ * for L2 / 128-byte descriptors (sfm_vocab_assign) and for binary / 32-byte descriptors
+ * (sfm_vocab_assign_hamming, with sfm_vocab_majority to refine the vocabulary); the stages after it
+ * work on word ids.  Everything is integer and exact: the outputs are a function of the inputs
+ * alone.
  *
  * sfm_vocab_assign: the nearest vocabulary word of every descriptor by exact squared L2, the
  * lowest word index among equal distances (i8 MFMA, the same contraction as sfm_match_batch).
@@ -585,6 +587,22 @@ int sfm_orb_batch(sfm_ctx* ctx, const uint8_t* images, int32_t n_img, int32_t H,
  *   vocab     [n_words][128] u8, 1 <= n_words <= 65536
  *   out_word  [n_img][k_max] i32: the word; -1 from n_kp[i] on
  *   out_dist  [n_img][k_max] i32 or NULL: that d^2; 0 where the word is -1
+ *
+ * sfm_vocab_assign_hamming: the same for 256-bit descriptors under Hamming distance (bits expanded
+ * to i8 on the MFMA).  Distances take 257 values, so ties are common: the lowest word index wins
+ * among equal distances, whatever the vocabulary size.
+ *   desc      [n_img][k_max][32] u8, 16-byte aligned; n_kp [n_img]; k_max <= 8192
+ *   vocab     [n_words][32] u8, 16-byte aligned, 1 <= n_words <= 65536
+ *   out_word  [n_img][k_max] i32: the word; -1 from n_kp[i] on
+ *   out_dist  [n_img][k_max] i32 or NULL: that distance in bits (0 .. 256); 0 where the word is -1
+ *
+ * sfm_vocab_majority: one k-majority round, out of place.  The members of word j are the rows
+ * q < n_kp[i] with word[i][q] == j (entries outside [0, n_words), -1 among them, are skipped).
+ * With cnt members of which ones[b] have bit b set (bit b = bit b % 8 of byte b / 8), bit b of
+ * out_vocab[j] is 1 if 2 ones[b] > cnt, bit b of vocab[j] if 2 ones[b] == cnt, else 0; a word
+ * without members keeps its bytes.  Integer counters in the context's workspace (n_words * 257
+ * u32, at most 64.25 MB); the result does not depend on block or atomic order.  1 <= n_words <=
+ * 65536, n_img * k_max < 2^32.  These two entry points are additive: sfm_version is unchanged.
  *
  * sfm_bow_hist: out_hist [n_img][n_words] u16 term frequencies of word [n_img][k_max] (entries
  * outside [0, n_words), -1 among them, and entries from n_kp[i] on are skipped).  The whole array
@@ -599,6 +617,12 @@ int sfm_orb_batch(sfm_ctx* ctx, const uint8_t* images, int32_t n_img, int32_t H,
 int sfm_vocab_assign(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, int32_t n_img,
                      int32_t k_max, const uint8_t* vocab, int32_t n_words, int32_t* out_word,
                      int32_t* out_dist);
+int sfm_vocab_assign_hamming(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, int32_t n_img,
+                             int32_t k_max, const uint8_t* vocab, int32_t n_words,
+                             int32_t* out_word, int32_t* out_dist);
+int sfm_vocab_majority(sfm_ctx* ctx, const uint8_t* desc, const int32_t* n_kp, int32_t n_img,
+                       int32_t k_max, const int32_t* word, const uint8_t* vocab, int32_t n_words,
+                       uint8_t* out_vocab);
 int sfm_bow_hist(sfm_ctx* ctx, const int32_t* word, const int32_t* n_kp, int32_t n_img,
                  int32_t k_max, int32_t n_words, uint16_t* out_hist);
 int sfm_bow_neighbours(sfm_ctx* ctx, const uint16_t* hist, int32_t n_img, int32_t n_words,

@@ -1,7 +1,9 @@
 // Image retrieval for pair selection: nearest vocabulary word of every
 // descriptor, per-image term frequencies, and the top-k images by weighted histogram intersection.
-// L2 / 128-byte descriptors only; everything is integer and exact, so every output is a function
-// of the inputs alone (no dependence on block or atomic order).
+// The assignment here is for L2 / 128-byte descriptors (retrieval_hamming.hip has the one for
+// binary descriptors; the other kernels work on word ids and serve both); everything is integer
+// and exact, so every output is a function of the inputs alone (no dependence on block or atomic
+// order).
 //
 // sfm_vocab_assign — the hot kernel, K1's exact i8 formulation with the vocabulary as the train
 // side.  With x' = x ^ 0x80 (u8 -> i8):  d^2(x, w) = |x'|^2 + |w'|^2 - 2 x'.w', so the nearest

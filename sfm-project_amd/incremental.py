@@ -269,7 +269,9 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     pairs: which image pairs are matched and verified.  None (the default): all of them.
     "retrieval": the pairs retrieval.select_pairs picks from the descriptors (vocabulary words,
     idf-weighted histogram intersection, each image's k best neighbours), with
-    `retrieval` a dict of its keyword arguments (k, n_words, seed, lloyd, vocab).  Or a caller's
+    `retrieval` a dict of its keyword arguments (k, n_words, seed, lloyd, vocab).  It takes
+    128-byte (L2) and 32-byte (binary, Hamming) descriptors; on binary ones keep the default
+    n_words or pass lloyd=2 (retrieval.py).  Or a caller's
     integer [P,2] array with 0 <= a < b < n_img, brought to sorted unique order.  The list is
     kept as rec.pairs and the time it took as rec.timings["select_pairs"]; it is deterministic,
     so under torch.distributed every rank computes the same list itself.

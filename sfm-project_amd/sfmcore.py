@@ -31,7 +31,8 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_match_cert_stats", "sfm_ransac_h_batch", "sfm_ransac_h_counts",
             "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid", "sfm_triangulate_robust",
             "sfm_triangulate_cam_table", "sfm_vocab_assign", "sfm_bow_hist",
-            "sfm_bow_neighbours", "sfm_guided_match_batch"]
+            "sfm_bow_neighbours", "sfm_guided_match_batch", "sfm_vocab_assign_hamming",
+            "sfm_vocab_majority"]
 
 
 class SfmCoreError(RuntimeError):
@@ -157,6 +158,8 @@ def load_library(path: str = LIB_PATH):
         L.sfm_graph_rows_packed.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
         L.sfm_graph_expand.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
         L.sfm_vocab_assign.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+        L.sfm_vocab_assign_hamming.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+        L.sfm_vocab_majority.argtypes = [vp, vp, vp, i32, i32, vp, vp, i32, vp]
         L.sfm_bow_hist.argtypes = [vp, vp, vp, i32, i32, i32, vp]
         L.sfm_bow_neighbours.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
         for name in EXPORTED:
@@ -286,12 +289,18 @@ class Context:
 
     # ---- image retrieval --------------------------------------------------------------------
     def vocab_assign(self, desc, n_kp, vocab, with_dist=True, out=None):
-        """Nearest vocabulary word of every descriptor (sfm_vocab_assign): desc [n_img,k_max,128]
-        u8, n_kp [n_img] i32, vocab [n_words,128] u8.  Returns (word [n_img,k_max] i32, -1 from
-        n_kp[i] on; dist [n_img,k_max] i32 squared L2, or None with with_dist=False)."""
+        """Nearest vocabulary word of every descriptor: desc [n_img,k_max,D] u8, n_kp [n_img] i32,
+        vocab [n_words,D] u8.  D = 128: exact squared L2 (sfm_vocab_assign); D = 32: Hamming
+        distance in bits (sfm_vocab_assign_hamming).  The lowest word index wins among equal
+        distances.  Returns (word [n_img,k_max] i32, -1 from n_kp[i] on; dist [n_img,k_max] i32,
+        0 where the word is -1, or None with with_dist=False)."""
         torch = self.torch
-        _expect("vocab_assign", ("desc", desc, torch.uint8, (desc.shape[1], 128)),
-                ("n_kp", n_kp, torch.int32, ()), ("vocab", vocab, torch.uint8, (128,)))
+        width = desc.shape[2] if desc.dim() == 3 else -1
+        if width not in (128, 32):
+            raise SfmCoreError("vocab_assign: desc must be [n_img, k_max, 128] u8 (L2) or "
+                               "[n_img, k_max, 32] u8 (Hamming)")
+        _expect("vocab_assign", ("desc", desc, torch.uint8, (desc.shape[1], width)),
+                ("n_kp", n_kp, torch.int32, ()), ("vocab", vocab, torch.uint8, (width,)))
         n_img, k_max = desc.shape[0], desc.shape[1]
         if n_kp.shape[0] != n_img:
             raise SfmCoreError("vocab_assign: desc / n_kp sizes differ")
@@ -306,9 +315,33 @@ class Context:
         if any(o.shape[0] != n_img for _, o, _, _ in specs):
             raise SfmCoreError("vocab_assign: out sizes differ from desc")
         self._bind_stream()
-        _check(self.lib.sfm_vocab_assign(self.handle, _ptr(desc), _ptr(n_kp), n_img, k_max,
-                                         _ptr(vocab), vocab.shape[0], _ptr(out[0]),
-                                         _ptr(out[1]) if out[1] is not None else None))
+        fn = self.lib.sfm_vocab_assign if width == 128 else self.lib.sfm_vocab_assign_hamming
+        _check(fn(self.handle, _ptr(desc), _ptr(n_kp), n_img, k_max, _ptr(vocab), vocab.shape[0],
+                  _ptr(out[0]), _ptr(out[1]) if out[1] is not None else None))
+        return out
+
+    def vocab_majority(self, desc, n_kp, word, vocab, out=None):
+        """One k-majority round (sfm_vocab_majority): desc [n_img,k_max,32] u8, n_kp [n_img] i32,
+        word [n_img,k_max] i32 (entries outside [0, n_words) and from n_kp[i] on are skipped),
+        vocab [n_words,32] u8.  Returns the new vocabulary [n_words,32] u8: per bit the majority
+        of the word's members, the old bit on an exact tie; a word without members keeps its
+        bytes."""
+        torch = self.torch
+        k_max = desc.shape[1] if desc.dim() == 3 else 0
+        _expect("vocab_majority", ("desc", desc, torch.uint8, (k_max, 32)),
+                ("n_kp", n_kp, torch.int32, ()), ("word", word, torch.int32, (k_max,)),
+                ("vocab", vocab, torch.uint8, (32,)))
+        n_img = desc.shape[0]
+        if n_kp.shape[0] != n_img or word.shape[0] != n_img:
+            raise SfmCoreError("vocab_majority: desc / n_kp / word sizes differ")
+        if out is None:
+            out = torch.empty_like(vocab)
+        _expect("vocab_majority", ("out", out, torch.uint8, (32,)))
+        if out.shape[0] != vocab.shape[0]:
+            raise SfmCoreError("vocab_majority: out size differs from vocab")
+        self._bind_stream()
+        _check(self.lib.sfm_vocab_majority(self.handle, _ptr(desc), _ptr(n_kp), n_img, k_max,
+                                           _ptr(word), _ptr(vocab), vocab.shape[0], _ptr(out)))
         return out
 
     def bow_hist(self, word, n_kp, n_words, out=None):
