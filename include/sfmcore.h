@@ -524,6 +524,41 @@ int sfm_triangulate_robust(sfm_ctx* ctx, int32_t n_cam, const double* cams, cons
                            const sfm_triangulate_robust_params* prm, double* out_pts,
                            double* out_stats, uint8_t* out_mask, int32_t* out_info);
 
+/* Recursive robust triangulation (the paper's §4.2: "run the RANSAC again on the
+ * measurements outside the consensus set"): a track that a wrong match merged out of several
+ * scene points gives one point per consensus set.  Inputs as sfm_triangulate_robust, plus n_obs,
+ * the length of cam_idx / uv / out_label (pt_ptr's values lie in 0 .. n_obs; it sizes the
+ * workspace, so that no count comes back to the host).  Per track, rounds r = 0 .. max_points-1:
+ * round r is sfm_triangulate_robust applied to the sub-track of the observations in no earlier
+ * round's mask, in CSR order, with the same pt_id and the seed seed + r (uint64 wrap-around);
+ * enumerated against sampled pairs, the refit, the re-score and the statistics all follow the
+ * sub-track.  Round 0 is taken as it comes (status 0, 1 or 4); a round r >= 1 is accepted iff
+ * its status is 0 and its consensus size is >= min_views; the first round not accepted ends the
+ * track.  A track's result depends on (seed, pt_id, its own observations) only.
+ *   out (device), R = max_points: pts [n_pt][R][3] f64, stats [n_pt][R][4] f64, info
+ *   [n_pt][R][2] i32: slot r < n_points holds round r's sfm_triangulate_robust outputs (slot 0
+ *   equals that call's, byte for byte); slot n_points is zero with info {0, -1} and the status
+ *   of the ending round: 1, 4, or 5 = consensus below min_views; later slots are zero, {0, -1},
+ *   status 5.  n_points [n_pt] i32: the accepted rounds (round 0 counts iff its status is 0).
+ *   label [n_obs] i8: the accepted round whose mask holds the observation, -1 for none
+ *   (observations outside every track's CSR range are not written).
+ * Every round is enqueued by the one call; nothing is read back in between. */
+typedef struct sfm_triangulate_multi_params {
+    int32_t struct_size; /* sizeof(sfm_triangulate_multi_params) of the caller */
+    int32_t max_points;  /* R: 1 .. 8 rounds per track */
+    int32_t min_views;   /* >= 2: smallest consensus of an accepted round r >= 1 */
+    int32_t max_hyp;     /* as sfm_triangulate_robust_params */
+    double thr;
+    double max_cos2;
+    uint64_t seed;
+} sfm_triangulate_multi_params;
+int sfm_triangulate_multi(sfm_ctx* ctx, int32_t n_cam, const double* cams, const double* pp,
+                          int32_t n_pt, const int32_t* pt_ptr, int32_t n_obs,
+                          const int32_t* cam_idx, const double* uv, const int32_t* pt_id,
+                          const sfm_triangulate_multi_params* prm, double* out_pts,
+                          double* out_stats, int32_t* out_info, int32_t* out_n_points,
+                          int8_t* out_label);
+
 /* The per-camera table both triangulation calls start from (device, out_tab [n_cam][20] f64 =
  * R (9, row-major), t (3), centre -R^T t (3), f, k1, pp (2), 0): what the fixed-order spec of
  * sfm_triangulate_robust takes as its input. */

@@ -1,4 +1,4 @@
-// Shared by the triangulation kernels (triangulate.hip, triangulate_robust.hip): the per-camera
+// Shared by the triangulation kernels (triangulate.hip, tri_robust_kernels.h): the per-camera
 // table, the fixed-point undistortion and the 4x4 Jacobi eigen-solver of the multi-view DLT.  One
 // definition, so both kernels execute the same operations in the same order.
 #pragma once

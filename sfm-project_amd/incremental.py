@@ -81,6 +81,9 @@ class Reconstruction:
         self._tracks = None
         self.obs_ok_d = None       # reconstruct(triangulation="ransac"): device [n_obs] bool, the
         #                            observation is still believed; .obs_ok is the host copy
+        self.split = None          # reconstruct(triangulation="ransac_split"): the keyword
+        #                            arguments of triangulate_multi (max_points, min_views)
+        self.n_split = 0           # tracks created out of later consensus sets
 
     @property
     def tracks(self):
@@ -235,7 +238,7 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
                 ba_iter=20, loss_s=2.0, device=0, log=None, group=None, shard_ba=False,
                 ba_cg_tol=0.1, ba_pcg="auto", ba_ftol=1e-6, init_pair="inliers",
                 init_candidates=64, triangulation="dlt", pairs=None, retrieval=None,
-                guided=None):
+                guided=None, split=None):
     """desc [n_img,K,D] u8, kps [n_img,K,2] pixels, n_kp [n_img], intr [n_img,4] = (f, k1, cx, cy).
     Returns a Reconstruction (cams [n_img,8], registered mask, points per track, track arrays).
     With torch.distributed initialised (one process per GPU, `group` or the default group) the
@@ -265,7 +268,13 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     rec.obs_ok_d / rec.obs_ok flag the observations still believed: one excluded by the
     triangulation's mask, or left above max_err by a bundle adjustment, stays out of the later
     adjustments, and a point with fewer than two believed observations in registered images is
-    dropped.
+    dropped.  "ransac_split": as "ransac", and sfm_triangulate_multi runs the RANSAC
+    again on the observations outside the consensus set (`split`: a dict of its max_points,
+    default 3, and min_views, default 2): a later consensus set that passes the acceptance test
+    of a new point becomes a track of its own with that point, ids continuing after the existing
+    tracks; rec.n_split counts them (a track that a wrong match merged out of two scene points
+    gives both).  rec.obs_d, rec.tracks, rec.points / has_point / obs_ok then cover the new tracks
+    too, still track-major.
     pairs: which image pairs are matched and verified.  None (the default): all of them.
     "retrieval": the pairs retrieval.select_pairs picks from the descriptors (vocabulary words,
     idf-weighted histogram intersection, each image's k best neighbours), with
@@ -283,10 +292,10 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     import torch
     if init_pair not in ("inliers", "pose"):
         raise ValueError(f"reconstruct: init_pair must be 'inliers' or 'pose', got {init_pair!r}")
-    if triangulation not in ("dlt", "ransac"):
-        raise ValueError(f"reconstruct: triangulation must be 'dlt' or 'ransac', "
+    if triangulation not in ("dlt", "ransac", "ransac_split"):
+        raise ValueError(f"reconstruct: triangulation must be 'dlt', 'ransac' or 'ransac_split', "
                          f"got {triangulation!r}")
-    robust = triangulation == "ransac"
+    robust = triangulation != "dlt"
     dev = torch.device("cuda", device)
     ctx = sfmcore.context(device)
     say = log or (lambda *a: None)
@@ -340,6 +349,8 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
     rec.cams[:, 6:8] = intr[:, :2]
     if robust:
         rec.obs_ok_d = torch.ones(obs_d[0].shape[0], dtype=torch.bool, device=dev)
+    if triangulation == "ransac_split":
+        rec.split = dict(dict(max_points=3, min_views=2), **(split or {}))
 
     # ---- initial pair: most verified inliers; relative pose from that pair's RANSAC-verified
     # matches (tracks may still carry a wrong observation), then its tracks are triangulated
@@ -399,7 +410,7 @@ def reconstruct(desc, kps, n_kp, intr, min_track=2, n_hyp=1024, reg_thr=4.0, max
         # 2-D/3-D correspondences of every unregistered image with >= 30 of them, grouped by
         # image (ascending) and ascending observation index within an image: one pass
         # (selected on the device from rec.obs_d: ~1.5 M observations at cfg5)
-        otr_d, timg_d, oxy_d = obs_d
+        otr_d, timg_d, oxy_d = rec.obs_d   # a split rebuilds them
         sel, ids, cptr = registration_obs(otr_d, timg_d, rec.has_d,
                                           torch.from_numpy(rec.registered).to(dev))
         if len(ids) == 0:
@@ -520,6 +531,9 @@ def _triangulate_new(rec, ctx, intr, max_err):
     sel = otr_d[reg_d[timg_d]]
     n_reg.index_add_(0, sel, torch.ones_like(sel))
     todo_d = torch.nonzero(~rec.has_d & (n_reg >= 2)).squeeze(1)
+    if rec.split is not None:
+        _triangulate_split(rec, ctx, intr, max_err, todo_d, reg_d)
+        return
     if todo_d.numel() == 0:
         return
     if rec.obs_ok_d is not None:
@@ -538,6 +552,117 @@ def _triangulate_new(rec, ctx, intr, max_err):
     ok = (st[:, 3] == 0) & (st[:, 0] < max_err) & (st[:, 1] > 1.0)
     rec.pts_d[todo_d[ok]] = pts[ok]
     rec.has_d[todo_d[ok]] = True
+
+
+def _triangulate_split(rec, ctx, intr, max_err, todo_d, reg_d):
+    """_triangulate_new under triangulation="ransac_split", through sfm_triangulate_multi.
+    1. The tracks todo_d (no point yet).  Slot 0 is handled as "ransac" handles its result.  Where
+       it is accepted, a slot r >= 1 that passes the same test (status 0, error < max_err, ray
+       angle > 1 degree) becomes a new track with that point: the observations labelled r move
+       to it.  What is left of an accepted track's observations in registered images (label -1
+       or a rejected slot) is no longer believed.
+    2. The tracks that had a point before (the initial pair's among them, which step 1 never
+       sees): their observations in registered images that the point does not explain (behind
+       the camera or off by max_err or more) are a sub-track of their own, and every slot of it
+       that passes the test becomes a new track."""
+    import torch
+    dev = reg_d.device
+    T = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x, dt)).to(dev)
+    cams_d, pp_d = T(rec.cams, np.float64), T(intr[:, 2:4], np.float64)
+    had_d = rec.has_d.clone()
+
+    def multi(tracks_d, o, ptr):
+        otr_d, timg_d, oxy_d = rec.obs_d
+        pts, st, _, _, label = ctx.triangulate_multi(cams_d, pp_d, ptr, timg_d[o].to(torch.int32),
+                                                     oxy_d[o].contiguous(),
+                                                     tracks_d.to(torch.int32), thr=max_err,
+                                                     **rec.split)
+        ok = (st[:, :, 3] == 0) & (st[:, :, 0] < max_err) & (st[:, :, 1] > 1.0)   # [n, R]
+        # per observation of o: its row of the call and its label
+        pos = torch.full((int(rec.has_d.numel()),), -1, dtype=torch.int64, device=dev)
+        pos[tracks_d] = torch.arange(tracks_d.numel(), device=dev)
+        return pts, ok, pos[otr_d[o]], label.long()
+
+    def spawn(new, pts, o, row, lab):
+        """The slots flagged in new [n, R] become tracks; returns the observations moved."""
+        moved = (lab >= 0) & new[row, lab.clamp(min=0)]
+        n_new = int(new.sum())                                  # the one sizing sync
+        if n_new:
+            n_tr = int(rec.has_d.numel())
+            slot_id = torch.full(new.shape, -1, dtype=torch.int64, device=dev)
+            slot_id[new] = n_tr + torch.arange(n_new, device=dev)   # (parent id, round) order
+            rec.obs_ok_d[o[moved]] = True
+            _move_observations(rec, o[moved], slot_id[row[moved], lab[moved]], pts[new])
+            rec.n_split += n_new
+
+    if todo_d.numel():
+        n_tr = int(rec.has_d.numel())
+        o, ptr = track_obs(rec.obs_d[0], rec.obs_d[1], n_tr, todo_d, reg_d)
+        pts, ok, row, lab = multi(todo_d, o, ptr)
+        ok0 = ok[:, 0]
+        rec.pts_d[todo_d[ok0]] = pts[ok0, 0]
+        rec.has_d[todo_d[ok0]] = True
+        new = ok & ok0[:, None]
+        new[:, 0] = False
+        moved = (lab >= 1) & new[row, lab.clamp(min=0)]
+        rec.obs_ok_d[o] = rec.obs_ok_d[o] & ~(ok0[row] & (lab != 0) & ~moved)   # no sizing sync
+        spawn(new, pts, o, row, lab)
+
+    otr_d, timg_d, oxy_d = rec.obs_d
+    n_tr = int(rec.has_d.numel())
+    had = torch.zeros(n_tr, dtype=torch.bool, device=dev)
+    had[:had_d.numel()] = had_d & rec.has_d[:had_d.numel()]
+    cand = torch.nonzero(had[otr_d] & reg_d[timg_d]).squeeze(1)
+    err, depth = _reprojection(cams_d, pp_d, rec.pts_d[otr_d[cand]], timg_d[cand], oxy_d[cand])
+    o = cand[~((depth > 0) & (err < max_err))]
+    cnt = torch.zeros(n_tr, dtype=torch.int64, device=dev)
+    cnt.index_add_(0, otr_d[o], torch.ones_like(o))
+    tracks_d = torch.nonzero(cnt >= 2).squeeze(1)
+    if tracks_d.numel() == 0:
+        return
+    o = o[cnt[otr_d[o]] >= 2]
+    ptr = torch.zeros(tracks_d.numel() + 1, dtype=torch.int32, device=dev)
+    ptr[1:] = torch.cumsum(cnt[tracks_d], 0)
+    pts, ok, row, lab = multi(tracks_d, o, ptr)
+    spawn(ok, pts, o, row, lab)
+
+
+def _reprojection(cams_d, pp_d, X, img, xy):
+    """Device (error in pixels, depth) of the points X [n, 3] in the images img [n] against the
+    keypoints xy [n, 2] under the full camera model (angle-axis, t, f, k1)."""
+    import torch
+    c = cams_d[img]
+    w = c[:, :3]
+    th = torch.linalg.norm(w, dim=1, keepdim=True)
+    k = w / th.clamp(min=1e-30)
+    P = (X * torch.cos(th) + torch.linalg.cross(k, X) * torch.sin(th)
+         + k * (k * X).sum(1, keepdim=True) * (1.0 - torch.cos(th))) + c[:, 3:6]
+    q = P[:, :2] / P[:, 2:3]
+    g = 1.0 + c[:, 7:8] * (q * q).sum(1, keepdim=True)
+    e = c[:, 6:7] * g * q + pp_d[img] - xy
+    return torch.linalg.norm(e, dim=1), P[:, 2]
+
+
+def _move_observations(rec, obs, track, new_pts):
+    """Appends len(new_pts) tracks with the points new_pts and moves the observations `obs` to
+    the tracks `track` (ids from the old track count on).  The observation arrays stay
+    track-major and contiguous, which the rest of the driver relies on: a stable device sort by
+    the new track id, applied to rec.obs_d, obs_ok_d and the tracks CSR; pts_d / has_d grow."""
+    import torch
+    otr_d, timg_d, oxy_d = rec.obs_d
+    ptr_t, img_t, kp_t = rec._tracks_d
+    n_all = int(rec.has_d.numel()) + int(new_pts.shape[0])
+    otr_new = otr_d.clone()
+    otr_new[obs] = track
+    otr_new, order = torch.sort(otr_new, stable=True)
+    rec.obs_d = (otr_new, timg_d[order], oxy_d[order])
+    rec.obs_ok_d = rec.obs_ok_d[order]
+    ptr_new = torch.zeros(n_all + 1, dtype=ptr_t.dtype, device=ptr_t.device)
+    ptr_new[1:] = torch.cumsum(torch.bincount(otr_new, minlength=n_all), 0)
+    rec._tracks_d, rec._tracks = (ptr_new, img_t[order], kp_t[order]), None
+    rec.pts_d = torch.cat([rec.pts_d, new_pts])
+    rec.has_d = torch.cat([rec.has_d, torch.ones(new_pts.shape[0], dtype=torch.bool,
+                                                 device=rec.has_d.device)])
 
 
 def _bundle(rec, intr, loss_s, ba_iter, max_err, device, shard_ba=False, group=None, cg_tol=0.1,

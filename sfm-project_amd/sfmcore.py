@@ -32,7 +32,7 @@ EXPORTED = ["sfm_ctx_create", "sfm_ctx_destroy", "sfm_ctx_set_stream", "sfm_ctx_
             "sfm_two_view_pose_batch", "sfm_l2fr_rev_grid", "sfm_triangulate_robust",
             "sfm_triangulate_cam_table", "sfm_vocab_assign", "sfm_bow_hist",
             "sfm_bow_neighbours", "sfm_guided_match_batch", "sfm_vocab_assign_hamming",
-            "sfm_vocab_majority"]
+            "sfm_vocab_majority", "sfm_triangulate_multi"]
 
 
 class SfmCoreError(RuntimeError):
@@ -77,6 +77,12 @@ class GuidedParams(C.Structure):
 class TriangulateRobustParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("max_hyp", C.c_int32), ("thr", C.c_double),
                 ("max_cos2", C.c_double), ("seed", C.c_uint64)]
+
+
+class TriangulateMultiParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_points", C.c_int32), ("min_views", C.c_int32),
+                ("max_hyp", C.c_int32), ("thr", C.c_double), ("max_cos2", C.c_double),
+                ("seed", C.c_uint64)]
 
 
 # stages of sfm_ba_solve_stage (include/sfmcore.h)
@@ -151,6 +157,8 @@ def load_library(path: str = LIB_PATH):
         L.sfm_triangulate.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
         L.sfm_triangulate_robust.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp,
                                              C.POINTER(TriangulateRobustParams), vp, vp, vp, vp]
+        L.sfm_triangulate_multi.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp,
+                                            C.POINTER(TriangulateMultiParams), vp, vp, vp, vp, vp]
         L.sfm_triangulate_cam_table.argtypes = [vp, i32, vp, vp, vp]
         L.sfm_tracks.argtypes = [vp, i32, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp]
         L.sfm_graph_offsets.argtypes = [vp, i32, vp, i32, vp]
@@ -842,6 +850,47 @@ class Context:
                                                _ptr(pt_id), C.byref(prm), _ptr(pts), _ptr(stats),
                                                _ptr(mask), _ptr(info)))
         return pts, stats, mask, info
+
+    def triangulate_multi(self, cams, pp, pt_ptr, cam_idx, uv, pt_id, max_points=3, min_views=2,
+                          thr=4.0, min_angle_deg=1.0, max_hyp=64, seed=42):
+        """Recursive robust triangulation (sfm_triangulate_multi): triangulate_robust again on the
+        observations outside the consensus set, up to max_points rounds per track, a round after
+        the first accepted with a consensus of >= min_views; all on the device.  Inputs as
+        triangulate_robust.  Returns device (pts [n_pt,R,3] f64, stats [n_pt,R,4] f64, info
+        [n_pt,R,2] i32, n_points [n_pt] i32, label [n_obs] i8 = the round whose point the
+        observation conforms to, -1 for none); see include/sfmcore.h."""
+        torch = self.torch
+        n_pt = max(pt_ptr.shape[0] - 1, 0)
+        _expect("triangulate_multi", ("cams", cams, torch.float64, (8,)),
+                ("pp", pp, torch.float64, (2,)), ("pt_ptr", pt_ptr, torch.int32, ()),
+                ("cam_idx", cam_idx, torch.int32, ()), ("uv", uv, torch.float64, (2,)),
+                ("pt_id", pt_id, torch.int32, ()))
+        if pp.shape[0] != cams.shape[0] or uv.shape[0] != cam_idx.shape[0]:
+            raise SfmCoreError("triangulate_multi: cams / pp or cam_idx / uv sizes differ")
+        if pt_id.shape[0] != n_pt:
+            raise SfmCoreError("triangulate_multi: pt_id must have one entry per track")
+        if not 0.0 <= float(min_angle_deg) < 90.0:
+            raise SfmCoreError("triangulate_multi: min_angle_deg must lie in [0, 90)")
+        R = int(max_points)
+        if not 1 <= R <= 8:
+            raise SfmCoreError("triangulate_multi: max_points must lie in 1 .. 8")
+        n_obs = cam_idx.shape[0]
+        dev = cams.device
+        pts = torch.empty((n_pt, R, 3), dtype=torch.float64, device=dev)
+        stats = torch.empty((n_pt, R, 4), dtype=torch.float64, device=dev)
+        info = torch.empty((n_pt, R, 2), dtype=torch.int32, device=dev)
+        n_points = torch.empty(n_pt, dtype=torch.int32, device=dev)
+        # observations outside every track's CSR range are never written
+        label = torch.full((n_obs,), -1, dtype=torch.int8, device=dev)
+        prm = TriangulateMultiParams(C.sizeof(TriangulateMultiParams), R, int(min_views),
+                                     int(max_hyp), float(thr), max_cos2_of(min_angle_deg),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._bind_stream()
+        _check(self.lib.sfm_triangulate_multi(self.handle, cams.shape[0], _ptr(cams), _ptr(pp),
+                                              n_pt, _ptr(pt_ptr), n_obs, _ptr(cam_idx), _ptr(uv),
+                                              _ptr(pt_id), C.byref(prm), _ptr(pts), _ptr(stats),
+                                              _ptr(info), _ptr(n_points), _ptr(label)))
+        return pts, stats, info, n_points, label
 
     def triangulate_cam_table(self, cams, pp):
         """The per-camera table [n_cam, 20] f64 the triangulation kernels start from
